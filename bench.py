@@ -17,7 +17,14 @@ pc_processor/utils/utils.py:21-44, tasks/pmf/trainer.py:33-39).  It fails loudly
 the launcher's WORLD_SIZE disagrees with --gpus.  Weak scaling (bs=2 per GPU); value = N*K iterations / max-over-ranks
 wall time.
 
-Extra objects on the JSON line (every mode: --mode infer, --backbone resnet50 ..., --model epmf carry them too):
+A plain run sets up, warms up, times the K steps and prints the result line.  --dump-outputs DIR also writes what the
+last timed step computed (loss and its terms and a fixed sample of the model state after the step; --mode infer: the KNN
+labels) as DIR/<name>.npy in float32; the inputs are seeded, so two builds can be compared output for output.
+
+Extra objects on the JSON line, with --full (every mode: --mode infer, --backbone resnet50 ..., --model epmf carry them
+too; each --no-* option leaves one out):
+  other_input_mode / parity / fp32_mfma_only -- the resident-address step rate, the timed plan against the CPU oracle,
+                  the same step with every convolution on fp32 MFMA (training).
   roofline     -- the dominant kernel, the conv MFMA kernel (conv_fwd_k: forward + input-gradient launches): algorithmic
                   FLOPs of those launches / their summed duration, measured with HIP events on the plan's stream in one
                   extra op-by-op iteration after the timed region; peak = 157.3 TFLOP/s fp32 MFMA (MI355X_MICROARCH.md).
@@ -48,6 +55,29 @@ ARITH_NOTE = ("fp32 in / fp32 out / fp32 accumulate; conv products of the pipeli
               "products of 3-way split operands (error of one fp32 rounding per product; PMF_CONV_F32=1 = fp32 MFMA only)")
 PEAK_BF16_MFMA = 2500.0     # TFLOP/s dense (MI355X_MICROARCH.md)
 PEAK_FP32_MFMA = 157.3                                # TFLOP/s, MI355X_MICROARCH.md
+DUMP_SAMPLE = 1 << 22       # --dump-outputs: positions of the model-state sample (at most 16 MB as float32)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy in float32"""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if torch.is_tensor(a):
+            a = a.detach().float().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float32).reshape(-1))
+
+
+def step_outputs(loss, terms, model):
+    """what a train step hands its caller: the loss, its terms, and the model state it leaves behind (every floating
+    parameter and buffer in state_dict order, flattened; above DUMP_SAMPLE elements a fixed seeded sample of positions)"""
+    out = {"loss": loss}
+    out.update(("loss_" + k, v) for k, v in terms.items())
+    state = torch.cat([t.detach().reshape(-1).float() for t in model.state_dict().values() if t.is_floating_point()])
+    if state.numel() > DUMP_SAMPLE:
+        idx = np.unique(np.random.default_rng(0).integers(0, state.numel(), DUMP_SAMPLE))
+        state = state[torch.from_numpy(idx).to(state.device)]
+    out["model_state_sample"] = state
+    return out
 
 
 def make_batch(bs, h, w, seed, device, nclasses=20):
@@ -102,6 +132,8 @@ def infer_bench(args, model, dev):
         out = step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"knn_labels": out})
     roof = hbm = cpu = parity = None
     if not args.no_roofline:
         plan = next(p for k, p in model._plans.items() if not k[3])
@@ -416,7 +448,7 @@ def salsanext_bench(args, dev, multi, rank, world):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss, _ = step()
+        loss, terms = step()
     torch.cuda.synchronize()
     if multi:
         dist.barrier()
@@ -427,6 +459,8 @@ def salsanext_bench(args, dev, multi, rank, world):
     dt = t.item()
     if not np.isfinite(float(loss)):
         raise SystemExit("bench.py: non-finite loss")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, step_outputs(loss, terms, model))
     if rank == 0:
         print(json.dumps({
             "metric": "train iters/sec SalsaNext %dx%d bs=%d (range loader + Lovasz/focal step)" % (args.height, args.width, args.bs),
@@ -958,18 +992,30 @@ def main():
                     help="time the step on ONE resident batch (same device addresses every iteration).  Default: a batch at "
                          "a NEW device address every iteration -- what DataLoader + .cuda() hands the reference's trainer "
                          "(tasks/pmf/trainer.py:289-303); the captured graphs keep replaying through the plan's own "
-                         "staging tensors.  The other mode's number is printed beside the headline either way")
+                         "staging tensors.  With --full the other mode's number is printed beside the headline")
     ap.add_argument("--knn-random-order", action="store_true",
                     help="--mode infer: KNN points in random order instead of sweep-file (azimuth-major) order")
-    ap.add_argument("--no-parity", action="store_true", help="skip the oracle parity block of the timed plan")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the other input mode, the oracle parity block, "
+                         "the rooflines and kernel-time breakdown, the fp32-MFMA-only step and the CPU baseline (each of "
+                         "them can still be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the oracle parity block of the timed plan")
     ap.add_argument("--parity-masked", action="store_true",
-                    help="parity block: also compare EVERY parameter gradient with the HIP path's activation decisions injected "
-                         "into the float64 / fp32 oracle passes (separates kinks from kernel defects)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-f32-ref", action="store_true", help="skip the fp32-MFMA-only reference measurement")
-    ap.add_argument("--profile-out", default=None, help="write the per-launch HIP-event profile (one line per op)")
+                    help="--full: parity block also compares EVERY parameter gradient with the HIP path's activation decisions "
+                         "injected into the float64 / fp32 oracle passes (separates kinks from kernel defects)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the rooflines and the kernel-time breakdown")
+    ap.add_argument("--no-f32-ref", action="store_true", help="--full: skip the fp32-MFMA-only reference measurement")
+    ap.add_argument("--profile-out", default=None, help="--full: write the per-launch HIP-event profile (one line per op)")
     args = ap.parse_args()
+    if not args.full:
+        if args.parity_masked or args.profile_out:
+            ap.error("--parity-masked and --profile-out belong to the extra measurements: add --full")
+        args.no_parity = args.no_cpu_baseline = args.no_roofline = args.no_f32_ref = True
+    if args.dump_outputs and args.mode == "loader":
+        ap.error("--dump-outputs: --mode loader has no step outputs to write")
 
     probe = os.environ.get("PMF_BENCH_DIST_PROBE") == "1"
     if args.gpus < 1:
@@ -1085,7 +1131,7 @@ def main():
     for i in range(args.steps):
         if i == args.steps // 2:
             ev[1].record()
-        loss, _ = step()
+        loss, terms = step()
     ev[2].record()
     torch.cuda.synchronize()
     if multi:
@@ -1143,24 +1189,29 @@ def main():
     loss_val = float(loss)
     if not np.isfinite(loss_val):
         raise SystemExit("bench.py: non-finite loss %r" % loss_val)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, step_outputs(loss, terms, model))
 
     # the other input mode, right behind the timed region (same process, same plan, warm clocks): all ranks take part
-    ko = max(1, min(10, args.steps))
-    for _ in range(2):
-        step(not args.fresh_inputs)
-    if multi:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(ko):
-        step(not args.fresh_inputs)
-    torch.cuda.synchronize()
-    if multi:
-        dist.barrier()
-    to = torch.tensor([time.perf_counter() - t1], device=dev, dtype=torch.float64)
-    if multi:
-        dist.all_reduce(to, op=dist.ReduceOp.MAX)
-    other_mode = {"fresh_input_addresses": not args.fresh_inputs, "value": world * ko / to.item(), "unit": "iter/s", "steps": ko}
+    ko, other_mode = 0, None
+    if args.full:
+        ko = max(1, min(10, args.steps))
+        for _ in range(2):
+            step(not args.fresh_inputs)
+        if multi:
+            dist.barrier()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(ko):
+            step(not args.fresh_inputs)
+        torch.cuda.synchronize()
+        if multi:
+            dist.barrier()
+        to = torch.tensor([time.perf_counter() - t1], device=dev, dtype=torch.float64)
+        if multi:
+            dist.all_reduce(to, op=dist.ReduceOp.MAX)
+        other_mode = {"fresh_input_addresses": not args.fresh_inputs, "value": world * ko / to.item(), "unit": "iter/s",
+                      "steps": ko}
 
     parity = None
     if rank == 0 and world == 1 and not args.no_parity:
@@ -1293,7 +1344,8 @@ def main():
                           if share_gpu or backend != "nccl" else {}),
                        "samples_per_s": world * args.bs * args.steps / dt, "final_loss": loss_val,
                        "fresh_input_addresses": bool(args.fresh_inputs),
-                       "init": "closed-form hash weights (pmf_amd.utils.detinit), %d training iterations before the parity block" % (args.warmup + args.steps + ko + 2),
+                       "init": "closed-form hash weights (pmf_amd.utils.detinit), %d training iterations before the parity block" % (
+                           args.warmup + args.steps + (ko + 2 if args.full else 0)),
                        "graphs_captured": len(next(iter(model._plans.values()))._graphs)},
             "warm_clock_check": halves, "data_parallel": per_rank,
             "parity": parity, "other_input_mode": other_mode,

@@ -268,7 +268,7 @@ def test_soak_300_iterations_then_gradient_bars():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ)
     env.pop("PMF_AUTOTUNE", None)               # the bench's default: shipped table + live tuning of unknown shapes
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "300", "--warmup", "5",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "300", "--warmup", "5", "--full",
                         "--no-cpu-baseline", "--no-f32-ref", "--no-roofline"], cwd=root, env=env, capture_output=True,
                        text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -297,9 +297,9 @@ def test_masked_backward_parity(steps, env, extra):
     e = dict(os.environ)
     e.pop("PMF_AUTOTUNE", None)
     e.update(env)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", str(steps), "--warmup", "3", "--parity-masked",
-                        "--no-cpu-baseline", "--no-f32-ref", "--no-roofline"] + extra, cwd=root, env=e, capture_output=True,
-                       text=True, timeout=1500)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", str(steps), "--warmup", "3", "--full",
+                        "--parity-masked", "--no-cpu-baseline", "--no-f32-ref", "--no-roofline"] + extra, cwd=root, env=e,
+                       capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     par = line["parity"]

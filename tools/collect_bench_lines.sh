@@ -6,7 +6,7 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/${TAG}_bench_lines.jsonl
 : > $OUT
 cd $ROOT
-run() { timeout 900 python bench.py "$@" 2> /dev/null | tail -1 >> $OUT; }
+run() { timeout 900 python bench.py --full "$@" 2> /dev/null | tail -1 >> $OUT; }
 run                                                   # headline (parity block, roofline, cpu_baseline, fp32_mfma_only)
 run --mode infer
 run --model epmf

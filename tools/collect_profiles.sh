@@ -10,10 +10,10 @@ cd /tmp; export TMPDIR=/tmp
 export PMF_TUNE_CACHE=/tmp/pmf_tune.txt        # same tile configurations in every pass
 python $ROOT/bench.py --steps 5 --warmup 3 --no-cpu-baseline --no-roofline --no-f32-ref --no-parity > $OUT/bench_plain.json 2> /dev/null
 # 1. per-kernel statistics of the default bench command
-rm -rf /tmp/p1; rocprofv3 --kernel-trace --stats -d /tmp/p1 -o r -- python $ROOT/bench.py --no-cpu-baseline --no-f32-ref > $OUT/bench_under_rocprof.json 2> /dev/null
+rm -rf /tmp/p1; rocprofv3 --kernel-trace --stats -d /tmp/p1 -o r -- python $ROOT/bench.py --full --no-cpu-baseline --no-f32-ref > $OUT/bench_under_rocprof.json 2> /dev/null
 python $ROOT/tools/rocpd_stats.py /tmp/p1/r_results.db $OUT/${TAG}_bench_kernel_stats.csv 0.5 > /dev/null
 # 2. per-layer kernel durations (one lane: launch order = op order)
-rm -rf /tmp/p2; PMF_LANES=0 rocprofv3 --kernel-trace -d /tmp/p2 -o j -- python $ROOT/bench.py --steps 10 --warmup 5 --no-cpu-baseline --no-f32-ref --no-parity --profile-out $OUT/ops.txt > /dev/null 2>&1
+rm -rf /tmp/p2; PMF_LANES=0 rocprofv3 --kernel-trace -d /tmp/p2 -o j -- python $ROOT/bench.py --full --steps 10 --warmup 5 --no-cpu-baseline --no-f32-ref --no-parity --profile-out $OUT/ops.txt > /dev/null 2>&1
 python $ROOT/tools/rocpd_join.py /tmp/p2/j_results.db $OUT/ops.txt 14 $OUT/${TAG}_per_layer_kernel_times.txt
 # (the same one-lane run as per-kernel statistics: every kernel alone on the chip -- what bench.py's roofline divides by)
 python $ROOT/tools/rocpd_stats.py /tmp/p2/j_results.db $OUT/${TAG}_bench_kernel_stats_one_lane.csv 0.5 > /dev/null
@@ -38,7 +38,7 @@ python $ROOT/tools/in_step.py /tmp/p2b/l_results.db /tmp/p4/m_results.db /tmp/p_
 # 6. per-layer kernel durations of the other BASELINE configurations (one lane): configs[3] PMF-ResNet50 32x1024, configs[4] EPMF
 for cfgname in r50 epmf; do
   if [ $cfgname = r50 ]; then ARGS="--backbone resnet50 --nclasses 17 --height 32 --width 1024"; else ARGS="--model epmf"; fi
-  rm -rf /tmp/p6; PMF_LANES=0 rocprofv3 --kernel-trace -d /tmp/p6 -o j -- python $ROOT/bench.py $ARGS --steps 10 --warmup 5 --no-cpu-baseline --no-f32-ref --no-parity --profile-out $OUT/ops_$cfgname.txt > /dev/null 2>&1
+  rm -rf /tmp/p6; PMF_LANES=0 rocprofv3 --kernel-trace -d /tmp/p6 -o j -- python $ROOT/bench.py --full $ARGS --steps 10 --warmup 5 --no-cpu-baseline --no-f32-ref --no-parity --profile-out $OUT/ops_$cfgname.txt > /dev/null 2>&1
   python $ROOT/tools/rocpd_join.py /tmp/p6/j_results.db $OUT/ops_$cfgname.txt 14 $OUT/${TAG}_per_layer_kernel_times_$cfgname.txt
 done
 ls -la $OUT

@@ -5,16 +5,16 @@ o=gpurun_out/r05z; mkdir -p $o
 python __graft_entry__.py smoke 2>&1 | tail -2
 bash tools/collect_profiles.sh r05 $1 > $o/collect.log 2>&1; head -1 gpurun_out/r05/r05_per_layer_kernel_times.txt
 L=$o/r05_bench_lines.jsonl; : > $L
-python bench.py --steps 20 --warmup 5 >> $L 2>/dev/null
-python bench.py --steps 100 --warmup 10 --no-cpu-baseline >> $L 2>/dev/null
-python bench.py --height 480 --width 640 --steps 30 --warmup 5 --no-cpu-baseline >> $L 2>/dev/null
-python bench.py --mode infer --steps 30 --warmup 5 --no-cpu-baseline >> $L 2>/dev/null
-python bench.py --mode infer --height 480 --width 640 --steps 30 --warmup 5 --no-cpu-baseline >> $L 2>/dev/null
-python bench.py --backbone resnet50 --nclasses 17 --height 32 --width 1024 --steps 50 --warmup 10 --no-cpu-baseline >> $L 2>/dev/null
-python bench.py --model epmf --steps 50 --warmup 10 --no-cpu-baseline >> $L 2>/dev/null
-python bench.py --model salsanext --steps 50 --warmup 10 --no-cpu-baseline >> $L 2>/dev/null
-python bench.py --height 256 --width 1024 --steps 30 --warmup 5 --no-cpu-baseline >> $L 2>/dev/null
-python bench.py --force-dist --steps 50 --warmup 10 --no-cpu-baseline --no-roofline --no-f32-ref >> $L 2>/dev/null
+python bench.py --full --steps 20 --warmup 5 >> $L 2>/dev/null
+python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline >> $L 2>/dev/null
+python bench.py --full --height 480 --width 640 --steps 30 --warmup 5 --no-cpu-baseline >> $L 2>/dev/null
+python bench.py --full --mode infer --steps 30 --warmup 5 --no-cpu-baseline >> $L 2>/dev/null
+python bench.py --full --mode infer --height 480 --width 640 --steps 30 --warmup 5 --no-cpu-baseline >> $L 2>/dev/null
+python bench.py --full --backbone resnet50 --nclasses 17 --height 32 --width 1024 --steps 50 --warmup 10 --no-cpu-baseline >> $L 2>/dev/null
+python bench.py --full --model epmf --steps 50 --warmup 10 --no-cpu-baseline >> $L 2>/dev/null
+python bench.py --full --model salsanext --steps 50 --warmup 10 --no-cpu-baseline >> $L 2>/dev/null
+python bench.py --full --height 256 --width 1024 --steps 30 --warmup 5 --no-cpu-baseline >> $L 2>/dev/null
+python bench.py --full --force-dist --steps 50 --warmup 10 --no-cpu-baseline --no-roofline --no-f32-ref >> $L 2>/dev/null
 python bench.py --mode loader >> $L 2>/dev/null
 python -c "
 import json
