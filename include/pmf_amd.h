@@ -597,6 +597,30 @@ int pmf_sgd_range(float* param, const float* grad, float* momentum_buffer, int64
  * feature tensor, C = 5); mask [N, HW]; mean / std [C].  Same float32 operation order as torch (bit-identical). */
 int pmf_normalise_inplace(float* x, int64_t stride_n, const float* mask, const float* mean, const float* stdv, int32_t N,
                           int32_t C, int64_t HW, pmf_stream_t s);
+/* ---- EPMF evaluation, one frame (tasks/epmf_eval_semantickitti/infer.py of the reference) -----------------------------
+ * The loader's frame proj f32[10,h,w] (depth, x, y, z, intensity, r, g, b, mask, label) is padded centred to
+ * H = ceil(h / 64) * 64, W likewise: top = (H - h) / 2, left = (W - w) / 2.
+ * pmf_eval_pre: pcd f32[5,H,W] = (x - mean) / stds * mask (float32, IEEE division), rgb f32[3,H,W] unnormalised, both zero
+ * padded; proj_depth f32[h,w] = depth - (depth == 0).  mean / stds: device float[5].  Bit-identical to the torch sequence. */
+int pmf_eval_pre(const float* proj, int32_t h, int32_t w, int32_t H, int32_t W, int32_t top, int32_t left,
+                 const float* mean, const float* stds, float* pcd, float* rgb, float* proj_depth, pmf_stream_t s);
+/* pmf_eval_argmax: class argmax of prob f32[C,H,W] over the window rows top..top+h-1, columns left..left+w-1 (ties -> lowest
+ * class, NaN wins: torch.argmax).  argmax (optional) int32[h,w]; conf (optional, C <= 64) int64[C][C] += (argmax, label)
+ * over the window pixels, label = f32[h,w] (proj channel 9); labels outside [0, C) are not counted. */
+int pmf_eval_argmax(const float* prob, int32_t C, int32_t H, int32_t W, int32_t top, int32_t left, int32_t h, int32_t w,
+                    const float* label, int32_t* argmax, int64_t* conf, pmf_stream_t s);
+/* pmf_eval_points: labels of the K kept points at box-relative pixels (x_data[k] - x_min, y_data[k] - y_min) (the int32
+ * truncated coordinates and bounding box of pmf_project_v2_index).  argmax == NULL: the argmax of the C probabilities at
+ * the point's pixel of the prob window (a point outside the window gets 0).  argmax != NULL: the KNN vote of
+ * pmf_knn_vote on that int32[h,w] map with proj_range f32[h,w], unproj_range f32[K] and knn_ws int64[3K + 2] of workspace.
+ * conf (optional, C <= 64) int64[C][C] += (label, lut[sem[src_idx[k]]]) (src_idx NULL: sem[k]; sem values outside the lut
+ * count as class 0).  labels (optional) int32[K]; labels_inv (optional) uint32[K] = lut_inv[label]. */
+int pmf_eval_points(const float* prob, int32_t C, int32_t H, int32_t W, int32_t top, int32_t left, int32_t h, int32_t w,
+                    const int32_t* x_data, const int32_t* y_data, int32_t x_min, int32_t y_min, int64_t K,
+                    const int32_t* argmax, const float* proj_range, const float* unproj_range, int32_t knn, int32_t search,
+                    const float* inv_gauss, float cutoff, int64_t* knn_ws, const int32_t* sem, const int32_t* src_idx,
+                    const int32_t* lut, int32_t nlut, int64_t* conf, const int32_t* lut_inv, int32_t nlut_inv,
+                    int32_t* labels, uint32_t* labels_inv, pmf_stream_t s);
 /* pixel splits pmf_conv_wgrad will use for this descriptor (sizes `partial`) */
 int pmf_conv_wgrad_nsplit(const pmf_wgrad_desc_t* d);
 /* sizeof() of the structs above, for bindings to self-check: 0 src, 1 conv, 2 wgrad, 3 view, 4 small, 5 op, 6 pack job */

@@ -28,6 +28,13 @@ static inline bool pmf_first_on_device(unsigned long long* mask) {
   return first;
 }
 
+// the KNN vote of knn.hip on an int64 (proj_argmax) or int32 (am32) label map, frames through the offsets table
+// (B >= 1); also called by eval.hip on the window argmax of one frame
+int knn_vote_batch_impl(const float* proj_range, const float* unproj_range, const int64_t* proj_argmax, const int32_t* am32,
+                        const int64_t* px, const int64_t* py, const int64_t* offsets, int32_t B, int32_t H, int32_t W,
+                        int64_t P_total, int32_t knn, int32_t search, const float* inv_gauss, float cutoff,
+                        int32_t nclasses, int64_t* labels, pmf_stream_t s);
+
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int round_up(int a, int b) { return cdiv(a, b) * b; }

@@ -1,0 +1,221 @@
+// EPMF point-wise evaluation on SemanticKITTI (tasks/epmf_eval_semantickitti/infer.py of the reference, per frame):
+// the device work around the network.  Frames have their own size (the bounding box of the yaw-cropped points), padded
+// centred up to multiples of 64; the reference spends ~10 small torch launches and host copies per frame on it.
+//   pmf_eval_pre     proj f32[10,h,w] -> pcd f32[5,H,W] = (x - mean) / std * mask, rgb f32[3,H,W], proj_depth f32[h,w]
+//   pmf_eval_argmax  class argmax over the (top, left, h, w) window of the padded probability map (row stride W, no
+//                    contiguous copy) -> optional int32[h,w] map, optional += [C][C] pixel confusion (pred, label)
+//   pmf_eval_points  labels of the K kept points: a gather of the argmax straight from the probability window, or the
+//                    KNN vote of knn.hip on the int32 map; += [C][C] point confusion, optional uint32 inverse-mapped ids
+// Ties of the argmax go to the lowest class and a NaN wins (torch.argmax).  Confusion counts are per-workgroup LDS
+// histograms flushed with 64-bit global atomics (as loss.hip's fused loss does); all stores are vector stores.
+#include "common.h"
+#pragma clang fp contract(off)
+
+#define EV_MAXC 64          // classes of an LDS confusion histogram (16 KB)
+#define EV_GRID 1024        // workgroup cap of the grid-stride kernels (bounds the histogram flushes)
+
+// ---- (a) frame -> network inputs -------------------------------------------------------------------------------------
+// One lane per pixel of the padded canvas; the torch sequence of the reference is ZeroPad2d, then
+// (x - mean) / std * mask in float32 (IEEE division: no reciprocal-multiply, no contraction), the same arithmetic here.
+__global__ __launch_bounds__(256) void eval_pre_k(const float* __restrict__ proj, int h, int w, int H, int W, int top,
+                                                  int left, const float* __restrict__ mean, const float* __restrict__ stds,
+                                                  float* __restrict__ pcd, float* __restrict__ rgb,
+                                                  float* __restrict__ pdepth) {
+  const int64_t HW = (int64_t)H * W, hw = (int64_t)h * w;
+  for (int64_t p = blockIdx.x * (int64_t)256 + threadIdx.x; p < HW; p += (int64_t)gridDim.x * 256) {
+    const int y = (int)(p / W), x = (int)(p - (int64_t)y * W);
+    const int r = y - top, c = x - left;
+    const bool in = r >= 0 && r < h && c >= 0 && c < w;
+    const int64_t q = in ? (int64_t)r * w + c : 0;
+    float v[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) v[k] = in ? proj[k * hw + q] : 0.f;
+    const float mk = v[8];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) pcd[k * HW + p] = (v[k] - mean[k]) / stds[k] * mk;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) rgb[k * HW + p] = v[5 + k];
+    if (in) pdepth[q] = v[0] - (v[0] == 0.f ? 1.f : 0.f);        // -1 on empty pixels (proj_depth.eq(0))
+  }
+}
+
+extern "C" int pmf_eval_pre(const float* proj, int32_t h, int32_t w, int32_t H, int32_t W, int32_t top, int32_t left,
+                            const float* mean, const float* stds, float* pcd, float* rgb, float* proj_depth,
+                            pmf_stream_t s) {
+  if (!proj || !mean || !stds || !pcd || !rgb || !proj_depth) return PMF_E_ARG;
+  if (h < 1 || w < 1 || top < 0 || left < 0 || top + h > H || left + w > W) return PMF_E_ARG;
+  const int64_t HW = (int64_t)H * W;
+  const int64_t g = cdiv64(HW, 256);
+  hipLaunchKernelGGL(eval_pre_k, dim3((unsigned)(g < 2048 ? g : 2048)), dim3(256), 0, (hipStream_t)s, proj, h, w, H, W,
+                     top, left, mean, stds, pcd, rgb, proj_depth);
+  PMF_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- (b) window argmax + pixel confusion -----------------------------------------------------------------------------
+__device__ __forceinline__ void ev_take(float v, int c, float& best, int& bi) {
+  const bool take = c == 0 || v > best || (v != v && best == best);     // torch.argmax: first maximum, NaN wins
+  best = take ? v : best;
+  bi = take ? c : bi;
+}
+
+__device__ __forceinline__ void ev_hist_zero(unsigned* hist, int C) {
+  for (int k = threadIdx.x; k < C * C; k += blockDim.x) hist[k] = 0u;
+  __syncthreads();
+}
+
+__device__ __forceinline__ void ev_hist_flush(const unsigned* hist, int C, unsigned long long* conf) {
+  __syncthreads();
+  for (int k = threadIdx.x; k < C * C; k += blockDim.x)
+    if (hist[k]) atomicAdd(conf + k, (unsigned long long)hist[k]);
+}
+
+// Four consecutive pixels of one row per lane, in groups aligned to the ABSOLUTE column (a multiple of 4 at or left of the
+// window's first column): with W % 4 == 0 and a 16-byte aligned map every group is one 16-byte load per class plane, for
+// any window offset, and stays inside its row of the padded map (columns outside the window are read, not used).  Other
+// maps read the four floats one by one.
+__global__ __launch_bounds__(256) void eval_argmax_k(const float* __restrict__ prob, int C, int H, int W, int top, int left,
+                                                     int h, int w, const float* __restrict__ label,
+                                                     int32_t* __restrict__ amap, unsigned long long* __restrict__ conf) {
+  __shared__ unsigned hist[EV_MAXC * EV_MAXC];
+  if (conf) ev_hist_zero(hist, C);
+  const int64_t HW = (int64_t)H * W;
+  const int a0 = left & ~3;
+  const int wq = (left + w - a0 + 3) >> 2;
+  const int64_t n4 = (int64_t)h * wq;
+  const bool vec = (W & 3) == 0 && (((uintptr_t)prob) & 15) == 0;
+  for (int64_t q = blockIdx.x * (int64_t)256 + threadIdx.x; q < n4; q += (int64_t)gridDim.x * 256) {
+    const int r = (int)(q / wq), a = a0 + (int)(q - (int64_t)r * wq) * 4;     // absolute column of the group
+    const float* base = prob + (int64_t)(top + r) * W + a;
+    float best[4] = {0.f, 0.f, 0.f, 0.f};
+    int bi[4] = {0, 0, 0, 0};
+    for (int c = 0; c < C; ++c) {
+      const float* pc = base + (int64_t)c * HW;
+      float v[4] = {0.f, 0.f, 0.f, 0.f};
+      if (vec) {
+        const f32x4 t = *(const f32x4*)pc;
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) if (a + k >= left && a + k < left + w) v[k] = pc[k];
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) ev_take(v[k], c, best[k], bi[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int col = a + k - left;
+      if (col < 0 || col >= w) continue;
+      const int64_t o = (int64_t)r * w + col;
+      if (amap) amap[o] = bi[k];
+      if (conf) {
+        const int t = (int)label[o];
+        if (t >= 0 && t < C) atomicAdd(&hist[bi[k] * C + t], 1u);
+      }
+    }
+  }
+  if (conf) ev_hist_flush(hist, C, conf);
+}
+
+static bool ev_window_ok(int C, int H, int W, int top, int left, int h, int w) {
+  return C >= 1 && h >= 1 && w >= 1 && top >= 0 && left >= 0 && top + h <= H && left + w <= W;
+}
+
+extern "C" int pmf_eval_argmax(const float* prob, int32_t C, int32_t H, int32_t W, int32_t top, int32_t left, int32_t h,
+                               int32_t w, const float* label, int32_t* argmax, int64_t* conf, pmf_stream_t s) {
+  if (!prob || !ev_window_ok(C, H, W, top, left, h, w)) return PMF_E_ARG;
+  if (conf && (!label || C > EV_MAXC)) return PMF_E_ARG;
+  if (!argmax && !conf) return 0;
+  const int64_t n4 = (int64_t)h * ((left + w - (left & ~3) + 3) >> 2);
+  const int64_t g = cdiv64(n4, 256);
+  hipLaunchKernelGGL(eval_argmax_k, dim3((unsigned)(g < EV_GRID ? g : EV_GRID)), dim3(256), 0, (hipStream_t)s, prob, C, H,
+                     W, top, left, h, w, label, argmax, (unsigned long long*)conf);
+  PMF_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- (c) point labels + point confusion ------------------------------------------------------------------------------
+// KNN path: the vote of knn.hip (knn_vote_batch_impl, one frame) reads int64 pixel coordinates and an offsets table:
+// px = column, py = row of the kept point inside the box (the reference's uproj_y_idx / uproj_x_idx).
+__global__ __launch_bounds__(256) void eval_knn_prep_k(const int32_t* __restrict__ xd, const int32_t* __restrict__ yd,
+                                                       int x_min, int y_min, int64_t K, int64_t* __restrict__ px,
+                                                       int64_t* __restrict__ py, int64_t* __restrict__ off) {
+  const int64_t k = blockIdx.x * (int64_t)256 + threadIdx.x;
+  if (k < K) {
+    px[k] = (int64_t)yd[k] - y_min;
+    py[k] = (int64_t)xd[k] - x_min;
+  }
+  if (k == 0) { off[0] = 0; off[1] = K; }
+}
+
+// One lane per kept point: its label (the vote's, or the argmax of the C probabilities at its pixel), the inverse-mapped
+// annotation id and the (pred, lut[sem[src]]) count.  Box-relative coordinates outside the window (not produced by the
+// loader: its box is the points' own) read nothing and give class 0.
+__global__ __launch_bounds__(256) void eval_points_k(const float* __restrict__ prob, int C, int H, int W, int top, int left,
+                                                     int h, int w, const int32_t* __restrict__ xd,
+                                                     const int32_t* __restrict__ yd, int x_min, int y_min, int64_t K,
+                                                     const int64_t* __restrict__ voted, const int32_t* __restrict__ sem,
+                                                     const int32_t* __restrict__ src, const int32_t* __restrict__ lut,
+                                                     int nlut, unsigned long long* __restrict__ conf,
+                                                     const int32_t* __restrict__ lut_inv, int nlut_inv,
+                                                     int32_t* __restrict__ labels, uint32_t* __restrict__ labels_inv) {
+  __shared__ unsigned hist[EV_MAXC * EV_MAXC];
+  if (conf) ev_hist_zero(hist, C);
+  const int64_t HW = (int64_t)H * W;
+  for (int64_t k = blockIdx.x * (int64_t)256 + threadIdx.x; k < K; k += (int64_t)gridDim.x * 256) {
+    int pred = 0;
+    if (voted) {
+      pred = (int)voted[k];
+    } else {
+      const int r = xd[k] - x_min, c = yd[k] - y_min;
+      if (r >= 0 && r < h && c >= 0 && c < w) {
+        const float* p = prob + (int64_t)(top + r) * W + left + c;
+        float best = 0.f;
+        for (int j = 0; j < C; ++j) ev_take(p[(int64_t)j * HW], j, best, pred);
+      }
+    }
+    if (labels) labels[k] = pred;
+    if (labels_inv) labels_inv[k] = (uint32_t)((pred >= 0 && pred < nlut_inv) ? lut_inv[pred] : 0);
+    if (conf) {
+      const int sl = sem[src ? src[k] : k];
+      const int t = (sl >= 0 && sl < nlut) ? lut[sl] : 0;
+      if (t >= 0 && t < C && pred >= 0 && pred < C) atomicAdd(&hist[pred * C + t], 1u);
+    }
+  }
+  if (conf) ev_hist_flush(hist, C, conf);
+}
+
+extern "C" int pmf_eval_points(const float* prob, int32_t C, int32_t H, int32_t W, int32_t top, int32_t left, int32_t h,
+                               int32_t w, const int32_t* x_data, const int32_t* y_data, int32_t x_min, int32_t y_min,
+                               int64_t K, const int32_t* argmax, const float* proj_range, const float* unproj_range,
+                               int32_t knn, int32_t search, const float* inv_gauss, float cutoff, int64_t* knn_ws,
+                               const int32_t* sem, const int32_t* src_idx, const int32_t* lut, int32_t nlut,
+                               int64_t* conf, const int32_t* lut_inv, int32_t nlut_inv, int32_t* labels,
+                               uint32_t* labels_inv, pmf_stream_t s) {
+  if (!ev_window_ok(C, H, W, top, left, h, w) || K < 0) return PMF_E_ARG;
+  if (K == 0) return 0;
+  if (!x_data || !y_data) return PMF_E_ARG;
+  if (conf && (!sem || !lut || nlut < 1 || C > EV_MAXC)) return PMF_E_ARG;
+  if (labels_inv && (!lut_inv || nlut_inv < 1)) return PMF_E_ARG;
+  hipStream_t st = (hipStream_t)s;
+  const int64_t* voted = nullptr;
+  if (argmax) {                                   // KNN: ws = px[K] | py[K] | offsets[2] | labels[K]
+    if (!proj_range || !unproj_range || !inv_gauss || !knn_ws) return PMF_E_ARG;
+    int64_t *px = knn_ws, *py = knn_ws + K, *off = knn_ws + 2 * K, *lab = knn_ws + 2 * K + 2;
+    hipLaunchKernelGGL(eval_knn_prep_k, dim3((unsigned)cdiv64(K, 256)), dim3(256), 0, st, x_data, y_data, x_min, y_min, K,
+                       px, py, off);
+    PMF_LAUNCH_CHECK();
+    const int rc = knn_vote_batch_impl(proj_range, unproj_range, nullptr, argmax, px, py, off, 1, h, w, K, knn, search,
+                                       inv_gauss, cutoff, C, lab, s);
+    if (rc != 0) return rc;
+    voted = lab;
+  } else if (!prob) {
+    return PMF_E_ARG;
+  }
+  const int64_t g = cdiv64(K, 256);
+  hipLaunchKernelGGL(eval_points_k, dim3((unsigned)(g < EV_GRID ? g : EV_GRID)), dim3(256), 0, st, prob, C, H, W, top,
+                     left, h, w, x_data, y_data, x_min, y_min, K, voted, sem, src_idx, lut, nlut,
+                     (unsigned long long*)conf, lut_inv, nlut_inv, labels, labels_inv);
+  PMF_LAUNCH_CHECK();
+  return 0;
+}

@@ -397,7 +397,7 @@ __global__ __launch_bounds__(256) void knn_batch_lds_k(const float* __restrict__
   labels[i] = best_cls;
 }
 
-static int knn_vote_batch_impl(const float* proj_range, const float* unproj_range, const int64_t* proj_argmax,
+int knn_vote_batch_impl(const float* proj_range, const float* unproj_range, const int64_t* proj_argmax,
                                const int32_t* am32, const int64_t* px, const int64_t* py, const int64_t* offsets, int32_t B,
                                int32_t H, int32_t W, int64_t P_total, int32_t knn, int32_t search, const float* inv_gauss,
                                float cutoff, int32_t nclasses, int64_t* labels, pmf_stream_t s) {

@@ -25,6 +25,15 @@ def project_frame_v2_gpu(points, sem_label, image_u8, proj_matrix, label_lut, fo
                          img_scale=1.0):
     """-> (proj f32[10,h,w], xy_index f64[K,2], depth f32[K], keep bool[P]) on `device`; img_scale multiplies the
     projected (row, col) coordinates (the caller passes the image already rescaled by it)."""
+    return _project_frame_v2(points, sem_label, image_u8, proj_matrix, label_lut, fov_left, fov_right, device,
+                             img_scale)[:4]
+
+
+def _project_frame_v2(points, sem_label, image_u8, proj_matrix, label_lut, fov_left, fov_right, device="cuda",
+                      img_scale=1.0):
+    """project_frame_v2_gpu + a dict of the device tensors the evaluation post path reads (postproc/frame_eval.py):
+    x_data / y_data int32[K] (truncated row / column), src int32[K] (source index of each kept point), sem int32[P],
+    lut int32, and the box corner x_min / y_min (host ints)."""
     lib = L.lib()
     dev = torch.device(device)
     from .perspective_view_loader import image_to_device
@@ -60,7 +69,8 @@ def project_frame_v2_gpu(points, sem_label, image_u8, proj_matrix, label_lut, fo
                                        depth.data_ptr(), k, img.data_ptr(), img.shape[0], img.shape[1], lut.data_ptr(),
                                        lut.shape[0], x_min, y_min, h, w, out.data_ptr(), pix.data_ptr(), st),
             "pmf_project_v2_scatter")
-    return out, xy[:k], depth[:k], keep[:P].bool()
+    extra = dict(x_data=xd[:k], y_data=yd[:k], src=src[:k], sem=sem, lut=lut, x_min=x_min, y_min=y_min)
+    return out, xy[:k], depth[:k], keep[:P].bool(), extra
 
 
 class PerspectiveViewLoaderV2(Dataset):
@@ -120,6 +130,22 @@ class PerspectiveViewLoaderV2(Dataset):
             return self.aug_ops(padded)
         top, lft = int(round((mh - ch) / 2.0)), int(round((mw - cw) / 2.0))            # CenterCrop (:36-39)
         return padded[:, top:top + ch, lft:lft + cw].contiguous()
+
+    def _eval_item(self, index):
+        """validation frame for the evaluation task (return_uproj layout): (proj, xy_index, depth, keep, extra) with
+        ``extra`` the device tensors of _project_frame_v2; the public return tuple of __getitem__ is unchanged."""
+        image = self.dataset.loadImage(index)
+        if self.img_jitter is not None:
+            from .perspective_view_loader import image_to_device
+            image = self.img_jitter(image_to_device(image, self.device))
+        if not isinstance(image, torch.Tensor):
+            image = np.asarray(image)
+        pointcloud, sem_label, _ = self.dataset.loadDataByIndex(index)
+        seq_id, _ = self.dataset.parsePathInfoByIndex(index)
+        fl = getattr(self.dataset, "fov_left", -45 / 180.0 * math.pi)
+        fr = getattr(self.dataset, "fov_right", 45 / 180.0 * math.pi)
+        return _project_frame_v2(pointcloud, sem_label, image, self.dataset.proj_matrix[seq_id],
+                                 self.dataset.class_map_lut, fl, fr, self.device)
 
     def __len__(self):
         if 0 < self.data_len < len(self.dataset):
