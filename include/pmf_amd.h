@@ -623,6 +623,19 @@ int pmf_eval_points(const float* prob, int32_t C, int32_t H, int32_t W, int32_t 
                     int32_t* labels, uint32_t* labels_inv, pmf_stream_t s);
 /* pixel splits pmf_conv_wgrad will use for this descriptor (sizes `partial`) */
 int pmf_conv_wgrad_nsplit(const pmf_wgrad_desc_t* d);
+/* the kernel family pmf_conv_wgrad runs for this descriptor under the current PMF_WG_* switches (the same selection that
+ * pmf_conv_wgrad_nsplit and the launch use; for tests and tools, nothing is launched) */
+int pmf_conv_wgrad_variant(const pmf_wgrad_desc_t* d);
+#define PMF_WG_UNIT 0       /* conv_wgrad_k: fp32 MFMA, output tiles dealt to the waves */
+#define PMF_WG_PIPE 1       /* conv_wgrad_pipe_k: fp32 MFMA, software-pipelined */
+#define PMF_WG_STAGED 2     /* conv_wgrad_s3_k: split-bf16, two barriers per tile (PMF_WG_SWP=0) */
+#define PMF_WG_SWP 3        /* conv_wgrad_s3_swp_k: split-bf16, software-pipelined, the waves split the pixels */
+#define PMF_WG_W8 4         /* conv_wgrad_s3_w8_k: split-bf16, eight waves (PMF_WG_W8=1) */
+#define PMF_WG_NSPLIT 5     /* conv_wgrad_s3n_k: split-bf16, the waves own different output-channel tiles */
+#define PMF_WG_DIRECT 6     /* wgrad_1x1_k: one tap, operands straight from global memory, fp32 MFMA */
+#define PMF_WG_DIRECT_S3 7  /* wgrad_1x1_s3_k: the same, split-bf16 */
+#define PMF_WG_STREAM 8     /* wgrad_stream_k: one tap, few channels, full-resolution maps */
+#define PMF_WG_FEWC 9       /* wgrad_fewc_k: <= 4 input channels (the 7x7 RGB stem) */
 /* sizeof() of the structs above, for bindings to self-check: 0 src, 1 conv, 2 wgrad, 3 view, 4 small, 5 op, 6 pack job */
 int pmf_sizeof(int which);
 

@@ -14,6 +14,8 @@ ACT_NONE, ACT_LRELU, ACT_RELU, ACT_SIGMOID = 0, 1, 2, 3
 SRC_RELU, SRC_BCAST = 1, 2
 EP_STAT_X_ONLY = 1
 WGRAD_S3 = 1
+# pmf_conv_wgrad_variant (PMF_WG_*)
+WG_UNIT, WG_PIPE, WG_STAGED, WG_SWP, WG_W8, WG_NSPLIT, WG_DIRECT, WG_DIRECT_S3, WG_STREAM, WG_FEWC = range(10)
 PMF_E_ARG, PMF_E_UNSUPPORTED = -1, -2
 CFG_DIRECT_TAPS = 1 << 24      # pmf_conv_desc_t.cfg: direct multi-tap variant (PMF_CFG_DIRECT_TAPS)
 CFG_WS = 1 << 25               # ... the wave-scheduled N-split kernel (PMF_CFG_WS, csrc/conv_ws.hip)
@@ -127,6 +129,8 @@ def lib():
     L.pmf_conv_wgrad.argtypes = [C.POINTER(WgradDesc), C.c_void_p]
     L.pmf_conv_wgrad_nsplit.restype = C.c_int
     L.pmf_conv_wgrad_nsplit.argtypes = [C.POINTER(WgradDesc)]
+    L.pmf_conv_wgrad_variant.restype = C.c_int
+    L.pmf_conv_wgrad_variant.argtypes = [C.POINTER(WgradDesc)]
     L.pmf_conv_wgrad_workspace.restype = C.c_int64
     L.pmf_conv_wgrad_workspace.argtypes = [C.POINTER(WgradDesc)]
     L.pmf_conv_multi_ok.restype = C.c_int
@@ -259,7 +263,7 @@ def lib():
 
 
 EXPORTS = [
-    "pmf_conv_fwd", "pmf_conv_wgrad", "pmf_conv_wgrad_partial", "pmf_conv_wgrad_reduce", "pmf_conv_wgrad_reduce_plan", "pmf_conv_wgrad_reduce_multi", "pmf_conv_wgrad_workspace", "pmf_conv_wgrad_nsplit", "pmf_pack_tile_ci",
+    "pmf_conv_fwd", "pmf_conv_wgrad", "pmf_conv_wgrad_partial", "pmf_conv_wgrad_reduce", "pmf_conv_wgrad_reduce_plan", "pmf_conv_wgrad_reduce_multi", "pmf_conv_wgrad_workspace", "pmf_conv_wgrad_nsplit", "pmf_conv_wgrad_variant", "pmf_pack_tile_ci",
     "pmf_pack_weights_batched", "pmf_conv_fwd_stat_rows", "pmf_conv_s3_eligible", "pmf_conv_ws_ok", "pmf_conv_fwd_stat_rows_max", "pmf_conv_fwd_kstages", "pmf_col_rows", "pmf_bn_finalize", "pmf_bn_eval_affine", "pmf_bn_bwd_reduce", "pmf_bn_bwd_fold", "pmf_bn_bwd_apply",
     "pmf_add_act", "pmf_add_act_bwd", "pmf_act_bwd", "pmf_avgpool3s2", "pmf_avgpool3s2_bwd", "pmf_maxpool3s2",
     "pmf_maxpool3s2_bwd", "pmf_bilinear2x", "pmf_bilinear2x_bwd", "pmf_pixel_shuffle2", "pmf_pixel_shuffle2_bwd",

@@ -2585,6 +2585,38 @@ __global__ __launch_bounds__(256) void wgrad_reduce_multi_k(const pmf_wgrad_desc
   else red_flat_body(jobs[lo], m.Ktot, m.Cout32, lb, m.gx);
 }
 
+// ---- host side: which kernel a descriptor runs ----------------------------------------------------------------------
+// Everything that depends on the kernel -- the template instantiation, the grid, the dynamic LDS and the split count that
+// sizes the partial-slab workspace -- is decided in ONE place, wg_pick(): pmf_conv_wgrad_nsplit (called by the plan at build
+// time), the launch and pmf_conv_wgrad_variant all read the same WgPick.  (A split count computed for another kernel than the
+// one launched is a workspace of the wrong size: a silent out-of-bounds write.)
+enum WgFamily {          // = PMF_WG_* of include/pmf_amd.h
+  WG_UNIT = PMF_WG_UNIT, WG_PIPE = PMF_WG_PIPE, WG_STAGED = PMF_WG_STAGED, WG_SWP = PMF_WG_SWP, WG_W8 = PMF_WG_W8,
+  WG_NSPLIT = PMF_WG_NSPLIT, WG_DIRECT = PMF_WG_DIRECT, WG_DIRECT_S3 = PMF_WG_DIRECT_S3, WG_STREAM = PMF_WG_STREAM,
+  WG_FEWC = PMF_WG_FEWC
+};
+struct WgPick {
+  int family;
+  int TB, NT;            // tiled families: taps per workgroup, 32-channel output tiles per workgroup (unit-dealing: 1 / 2 / 4)
+  int XSL;               // 16-byte input-tile slots per thread (7 / 9; eight-wave: 4 / 5)
+  int NCO, RAG;          // N-split: output-channel tiles per workgroup, partial 4 x 32-pixel tiles; direct 1x1 fp32: NCO
+  int KG;                // few-channel: row tiles of 32 (tap, channel) pairs
+  int KT, NTL;           // streaming: 32-row / 32-column tiles
+  WgGeom g;
+  int block, lds;        // threads, dynamic LDS bytes
+  int gy, gz;            // grid = (nsplit, gy, gz)
+  // default split count = max(1, min(target / per_split, cap)) * mult
+  int target, per_split, cap, mult;
+};
+
+static void wg_tap_extent(const pmf_wgrad_desc_t* d, int* dy_min, int* dy_max, int* dx_min, int* dx_max) {
+  *dy_min = *dx_min = 127; *dy_max = *dx_max = -127;
+  for (int t = 0; t < d->ntaps; ++t) {
+    *dy_min = d->tdy[t] < *dy_min ? d->tdy[t] : *dy_min; *dy_max = d->tdy[t] > *dy_max ? d->tdy[t] : *dy_max;
+    *dx_min = d->tdx[t] < *dx_min ? d->tdx[t] : *dx_min; *dx_max = d->tdx[t] > *dx_max ? d->tdx[t] : *dx_max;
+  }
+}
+
 static int wg_geometry(const pmf_wgrad_desc_t* d, int TB, int BN, WgGeom* g, int* lds) {
   int Ktot = 0, nchunks = 0;
   for (int i = 0; i < d->nsrc; ++i) { Ktot += d->src[i].C; nchunks += cdiv(d->src[i].C, WG_CI); }
@@ -2592,11 +2624,8 @@ static int wg_geometry(const pmf_wgrad_desc_t* d, int TB, int BN, WgGeom* g, int
   g->Cout32 = round_up(d->Cout, 32);
   g->tiles_x = cdiv(d->OW, 32); g->tiles_y = cdiv(d->OH, WG_ROWS);
   g->total_tiles = g->tiles_x * g->tiles_y * d->N;
-  int dy_min = 127, dy_max = -127, dx_min = 127, dx_max = -127;
-  for (int t = 0; t < d->ntaps; ++t) {
-    dy_min = d->tdy[t] < dy_min ? d->tdy[t] : dy_min; dy_max = d->tdy[t] > dy_max ? d->tdy[t] : dy_max;
-    dx_min = d->tdx[t] < dx_min ? d->tdx[t] : dx_min; dx_max = d->tdx[t] > dx_max ? d->tdx[t] : dx_max;
-  }
+  int dy_min, dy_max, dx_min, dx_max;
+  wg_tap_extent(d, &dy_min, &dy_max, &dx_min, &dx_max);
   g->dy_min = dy_min; g->dx_min = dx_min;
   int rows = (WG_ROWS - 1) * d->in_stride + 1, cols = 31 * d->in_stride + 1;
   if (!d->gather) { rows += dy_max - dy_min; cols += dx_max - dx_min; }
@@ -2625,77 +2654,119 @@ static bool wg_simple(const pmf_wgrad_desc_t* d, const WgGeom& g, int TB, int BN
   return true;
 }
 
-// taps per workgroup (TB) and output-channel tiles (NT): 3x3 -> 9 taps, 2x2 -> 4, per-tap staging -> 1.
-// Pipelined kernel (when its conditions hold): NT = 1 -- every wave carries all TB taps of one 32-channel tile, the
-// narrow tile keeps the split count (hence the partial-slab traffic) low and measured fastest at every resolution.
-// Unit-dealing kernel: 64 output channels per workgroup (2 waves/SIMD fit; 128 measured slower).
-static int wg_s3n_nco(const pmf_wgrad_desc_t* d, const WgGeom& g, int TB);
-static void wg_config(const pmf_wgrad_desc_t* d, int* TB, int* NT) {
-  if (d->gather || d->ntaps == 1) *TB = 1;
-  else if (d->ntaps <= 4) *TB = 4;
-  else *TB = 9;
-  WgGeom g;
-  int lds;
-  wg_geometry(d, *TB, 32, &g, &lds);
-  // 1x1 convolutions with wide outputs are plain GEMMs: one MFMA per operand pair either way, so the wider tile of
-  // the unit-dealing kernel (fewer re-reads of the input tile) wins there (measured 123 vs 164 us on 384 -> 128)
-  const bool wide_1x1 = d->ntaps == 1 && d->Cout > 64;
-  const int cmod = (d->flags & PMF_WGRAD_S3) ? 16 : WG_CI;
-  if (d->cfg) {                        // caller-tuned
-    int nt = d->cfg & 0xff;
-    const int kern = (d->cfg >> 8) & 0xff;
-    if (nt != 1 && nt != 2 && nt != 4) nt = 1;
-    if (nt == 4 && *TB != 1) nt = 2;                        // 128-wide tiles are only built for per-tap staging
-    while (nt > 1 && (nt - 1) * 32 >= d->Cout) nt >>= 1;
-    if (kern == 1 && wg_simple(d, g, *TB, 32, cmod)) nt = 1;
-    *NT = nt;
-    return;
-  }
-  if (!wide_1x1 && wg_simple(d, g, *TB, 32, cmod)) { *NT = 1; return; }
-  if (!wide_1x1 && wg_s3n_nco(d, g, *TB) > 0) { *NT = 1; return; }   // ragged tiles / last channel tile
-  *NT = wide_1x1 ? 4 : (d->Cout > 32 ? 2 : 1);
+// few-input-channel path (ResNet stem): conditions
+static bool wg_fewc(const pmf_wgrad_desc_t* d) {
+  if (d->nsrc != 1 || d->in_stride != 1 || d->Cin_real > 4 || d->ntaps < 9) return false;
+  if (d->ntaps * d->Cin_real > 160 || d->Cout % 64 || d->OH % WG_ROWS || d->OW % 32) return false;
+  if (d->src[0].flags || d->src[0].scale || d->src[0].cmul) return false;        // raw input only
+  if (d->src[0].H != d->OH || d->src[0].W != d->OW) return false;
+  return true;
 }
 
-// output-channel tiles per workgroup of the N-split split-bf16 kernel (conv_wgrad_s3n_k): 4 / 2, or 0 = not this kernel.
-// PMF_WG_S3N=0 switches it off (A/B), =2 caps it at two tiles.
-static int wg_s3n_nco(const pmf_wgrad_desc_t* d, const WgGeom& g, int TB) {
-  const char* e_n = getenv("PMF_WG_S3N");     // (read per call, not cached: the tests switch variants)
-  const int mode = e_n ? atoi(e_n) : 4;
+// output-channel tiles per workgroup of the N-split split-bf16 kernel (conv_wgrad_s3n_k): 4 / 2 / 1, or 0 = not this kernel.
+// mode = PMF_WG_S3N: 0 switches it off (A/B), 2 caps it at two tiles.
+static int wg_s3n_nco(const pmf_wgrad_desc_t* d, const WgGeom& g, int TB, int mode, bool older) {
   // (operands of 8 channels too -- EPMF's 3x3 5 -> 32 first layer, padded to 8: a quarter-full chunk; the rows of the 32-row
   // tile beyond the operand's channels are staged as zeros and never written to the slab)
   if (mode <= 1 || TB <= 1 || !(d->flags & PMF_WGRAD_S3) || !wg_simple(d, g, TB, 32, 8, true)) return 0;
   if ((int64_t)d->N * d->OH * d->OW * d->dz_ldc * 4 >= (1ll << 31)) return 0;
-  const char* e_w8 = getenv("PMF_WG_W8");
-  const char* e_swp = getenv("PMF_WG_SWP");
-  if ((e_w8 && e_w8[0] == '1') || (e_swp && e_swp[0] == '0')) return 0;        // the test switches for the older variants
+  if (older) return 0;                                 // the test switches for the older variants
   if (d->Cout % 32) return mode == 3 ? 0 : 1;          // ragged last tile: one tile per workgroup
   if (mode >= 4 && d->Cout % 128 == 0) return 4;
   if (d->Cout % 64 == 0) return 2;
   return mode == 3 ? 0 : 1;       // (3: 32-channel tiles on the round-3 software-pipelined kernel)
 }
 
-static bool wg_fewc(const pmf_wgrad_desc_t* d);
-extern "C" int pmf_conv_wgrad_nsplit(const pmf_wgrad_desc_t* d) {
-  if (wg_fewc(d)) {   // one output-channel tile pair per workgroup: split the pixel tiles 256 ways
-    const int tiles = cdiv(d->OW, 32) * cdiv(d->OH, WG_ROWS) * d->N, ns = 256 / cdiv(d->Cout, 64);
-    return tiles < ns ? tiles : (ns < 1 ? 1 : ns);
+static void wg_pick(const pmf_wgrad_desc_t* d, WgPick* p) {
+  *p = WgPick{};
+  p->block = 256; p->gy = p->gz = 1; p->mult = 1;
+  int lds;
+  if (wg_fewc(d)) {      // one output-channel tile pair per workgroup: split the pixel tiles 256 ways
+    wg_geometry(d, 1, 64, &p->g, &lds);
+    int dy_min, dy_max, dx_min, dx_max;
+    wg_tap_extent(d, &dy_min, &dy_max, &dx_min, &dx_max);
+    WgGeom& g = p->g;
+    g.in_rows = WG_ROWS + dy_max - dy_min; g.in_cols = 32 + dx_max - dx_min;   // always a halo tile here
+    g.co_tiles = d->Cout / 64; g.tap_batches = 1;
+    const int xfl = (g.in_rows * g.in_cols * d->Cin_real + 4 + 3) & ~3;
+    const int kg = cdiv(d->ntaps * d->Cin_real, 32);
+    p->family = WG_FEWC; p->KG = kg <= 3 ? (kg < 1 ? 1 : kg) : 5;
+    p->lds = (xfl + 2 * 64 * 64) * 4 < 16 * 1024 ? 16 * 1024 : (xfl + 2 * 64 * 64) * 4;
+    p->gz = g.co_tiles;
+    p->target = 256; p->per_split = cdiv(d->Cout, 64); p->cap = g.total_tiles;
+    return;
   }
-  if (wg_stream(d)) return d->N * wg_stream_splits(d);
+  wg_geometry(d, 1, 32, &p->g, &lds);
+  const int64_t pairs = ((int64_t)d->N * d->OH * d->OW + 1) / 2;
+  if (wg_stream(d)) {    // N x S workgroups, one sample each, >= 64 pixel pairs per workgroup
+    p->family = WG_STREAM; p->KT = cdiv(p->g.Ktot, 32); p->NTL = p->g.Cout32 / 32;
+    p->target = 512; p->per_split = p->mult = d->N > 0 ? d->N : 1; p->cap = (d->OH * d->OW + 1) / 2 / 64;
+    return;
+  }
   if (wg_direct_1x1(d)) {  // two resident workgroups per CU in total; every workgroup gets >= 64 pixel pairs
-    int kb, ob, nco;
-    wg_direct_grid(d, &kb, &ob, &nco);
-    constexpr int dtarget = 512;
-    int ns = dtarget / (kb * ob);
-    const int64_t pairs = ((int64_t)d->N * d->OH * d->OW + 1) / 2;
-    if (ns > pairs / 64) ns = (int)(pairs / 64);
-    return ns < 1 ? 1 : ns;
+    wg_direct_grid(d, &p->gy, &p->gz, &p->NCO);
+    p->family = wg_direct_s3(d) ? WG_DIRECT_S3 : WG_DIRECT;
+    p->lds = (p->family == WG_DIRECT && p->NCO == 2 ? 8 : 4) * 16 * 64 * 4;
+    p->target = 512; p->per_split = p->gy * p->gz; p->cap = (int)(pairs / 64 < 0x7fffffff ? pairs / 64 : 0x7fffffff);
+    return;
   }
-  int TB, NT, lds;
-  WgGeom g;
-  wg_config(d, &TB, &NT);
+  // ---- tiled kernels.  Taps per workgroup (TB): 3x3 -> 9 taps, 2x2 -> 4, per-tap staging -> 1; output-channel tiles (NT).
+  // Pipelined kernels (when their conditions hold): NT = 1 -- every wave carries all TB taps of one 32-channel tile, the
+  // narrow tile keeps the split count (hence the partial-slab traffic) low and measured fastest at every resolution.
+  // Unit-dealing kernel: 64 output channels per workgroup (2 waves/SIMD fit; 128 measured slower).
+  // The variant switches are read per call, not cached: the tests flip them inside one process (a replayed graph never
+  // comes here).
+  const char* e_n = getenv("PMF_WG_S3N");
+  const char* e_swp = getenv("PMF_WG_SWP");
+  const char* e_w8 = getenv("PMF_WG_W8");
+  const bool swp = !(e_swp && e_swp[0] == '0'), w8 = e_w8 && e_w8[0] == '1';
+  const int TB = (d->gather || d->ntaps == 1) ? 1 : (d->ntaps <= 4 ? 4 : 9);
+  WgGeom& g = p->g;
+  wg_geometry(d, TB, 32, &g, &lds);
+  const bool s3 = (d->flags & PMF_WGRAD_S3) != 0;
+  const int kern = (d->cfg >> 8) & 0xff;
+  const bool simple = wg_simple(d, g, TB, 32, s3 ? 16 : WG_CI);
+  const int nco = wg_s3n_nco(d, g, TB, e_n ? atoi(e_n) : 4, w8 || !swp);      // (> 0: ragged tiles / last channel tile too)
+  // 1x1 convolutions with wide outputs are plain GEMMs: one MFMA per operand pair either way, so the wider tile of
+  // the unit-dealing kernel (fewer re-reads of the input tile) wins there (measured 123 vs 164 us on 384 -> 128)
+  const bool wide_1x1 = d->ntaps == 1 && d->Cout > 64;
+  int NT;
+  if (d->cfg) {                        // caller-tuned
+    NT = d->cfg & 0xff;
+    if (NT != 1 && NT != 2 && NT != 4) NT = 1;
+    if (NT == 4 && TB != 1) NT = 2;                        // 128-wide tiles are only built for per-tap staging
+    while (NT > 1 && (NT - 1) * 32 >= d->Cout) NT >>= 1;
+    if (kern == 1 && simple) NT = 1;
+  } else if (!wide_1x1 && (simple || nco > 0)) NT = 1;
+  else NT = wide_1x1 ? 4 : (d->Cout > 32 ? 2 : 1);
   wg_geometry(d, TB, NT * 32, &g, &lds);
-  int other = g.nchunks * g.co_tiles * g.tap_batches;
-  if (NT == 1) { const int nco = wg_s3n_nco(d, g, TB); if (nco) other = g.nchunks * cdiv(d->Cout, 32 * nco); }
+  p->family = WG_UNIT; p->TB = TB; p->NT = NT; p->lds = lds;
+  p->gy = g.nchunks; p->gz = g.co_tiles * g.tap_batches;
+  const int slots = g.in_rows * g.in_cols * 8;             // 16-byte slots of the input tile
+  p->XSL = slots <= 256 * 7 ? 7 : 9;
+  if (NT == 1 && s3 && (simple || nco)) {
+    g.x_floats = g.in_rows * g.in_cols * (WS3_XPB / 4);
+    const int xdb = 2 * (g.x_floats + WS3_XPB / 4);        // double-buffered, + the spare pixel that slots beyond the tile write to
+    if (nco) {
+      p->family = WG_NSPLIT; p->NCO = nco; p->RAG = d->OH % WG_ROWS || d->OW % 32;
+      p->lds = xdb * 4; p->gz = cdiv(d->Cout, 32 * nco);
+    } else if (swp && w8 && TB > 1) {
+      // eight waves (the taps of a slab on two waves, two waves per SIMD): 3-10 % faster launch by launch, but 110 KiB
+      // of LDS and 512 threads leave no room for the input-gradient launches the weight gradients run next to:
+      // 16.08 vs 15.97 ms per step -- off unless PMF_WG_W8=1
+      p->family = WG_W8; p->block = 512; p->XSL = slots <= 512 * 4 ? 4 : 5;
+      p->lds = (xdb + 3 * WG_ROWS * 32 * 32) * 4;
+    } else if (swp) {    // input tile double-buffered: tile t + 1 is split while tile t is multiplied
+      p->family = WG_SWP; p->lds = (xdb + WG_ROWS * 32 * 32) * 4;
+    } else {
+      p->family = WG_STAGED; p->lds = (g.x_floats + WG_ROWS * 32 * 32) * 4;
+    }
+    if (p->family != WG_STAGED) g.x_floats += WS3_XPB / 4;
+    if (p->lds < 16 * 1024) p->lds = 16 * 1024;            // room for the pixel-group fold
+  } else if (NT == 1 && wg_simple(d, g, TB, 32) && kern != 2) {
+    p->family = WG_PIPE;
+    if (p->lds < 16 * 1024) p->lds = 16 * 1024;            // room for the pixel-group reduction
+  }
   // workgroups per launch: one per TWO CUs.  More make the launch itself faster in isolation (512: 4.8 ms over the 110 layers,
   // 256: 5.4 ms), but the weight gradients run on side lanes next to the input-gradient launches of the main lane -- which IS
   // the step -- and a weight-gradient workgroup holds 80-110 KiB of its CU's LDS: with one on every CU a main-lane conv
@@ -2704,10 +2775,21 @@ extern "C" int pmf_conv_wgrad_nsplit(const pmf_wgrad_desc_t* d) {
   // PMF-ResNet50 32x1024 10.07 -> 9.79 ms, EPMF 14.66 -> 14.61, SalsaNext 11.33 -> 11.22.  Half the partial slabs is also half
   // the stage-2 traffic.  PMF_WGRAD_WGS overrides.
   static const int target = getenv("PMF_WGRAD_WGS") ? atoi(getenv("PMF_WGRAD_WGS")) : 128;
-  int ns = target / (other > 0 ? other : 1);
-  if (ns < 1) ns = 1;
-  if (ns > g.total_tiles) ns = g.total_tiles;
-  return ns;
+  p->target = target; p->per_split = p->gy * p->gz > 0 ? p->gy * p->gz : 1; p->cap = g.total_tiles;
+}
+
+extern "C" int pmf_conv_wgrad_variant(const pmf_wgrad_desc_t* d) {
+  WgPick p;
+  wg_pick(d, &p);
+  return p.family;
+}
+
+extern "C" int pmf_conv_wgrad_nsplit(const pmf_wgrad_desc_t* d) {
+  WgPick p;
+  wg_pick(d, &p);
+  int ns = p.target / p.per_split;
+  if (ns > p.cap) ns = p.cap;
+  return (ns < 1 ? 1 : ns) * p.mult;
 }
 
 extern "C" int64_t pmf_conv_wgrad_workspace(const pmf_wgrad_desc_t* d) {
@@ -2758,216 +2840,90 @@ extern "C" int pmf_conv_wgrad_reduce_multi(const pmf_wgrad_desc_t* jobs_dev, con
   return 0;
 }
 
-template <int TB, int NT>
-static int wg_launch(const pmf_wgrad_desc_t* d, hipStream_t s, int phase) {
-  WgGeom g;
-  int lds;
-  wg_geometry(d, TB, NT * 32, &g, &lds);
-  if (lds > 160 * 1024) return PMF_E_UNSUPPORTED;
-  if (!(phase & 1)) return wg_reduce(d, g, s);
-  static unsigned long long attr_set = 0ull;
-  if (pmf_first_on_device(&attr_set)) {
-    (void)hipFuncSetAttribute((const void*)conv_wgrad_k<TB, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if constexpr (NT == 1) {
-      (void)hipFuncSetAttribute((const void*)conv_wgrad_pipe_k<TB, 1, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void)hipFuncSetAttribute((const void*)conv_wgrad_pipe_k<TB, 1, 9>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
-  }
-  dim3 grid(d->nsplit, g.nchunks, g.co_tiles * g.tap_batches);
-  bool piped = false;
-  if constexpr (NT == 1) {
-    if ((d->flags & PMF_WGRAD_S3) && (wg_simple(d, g, TB, 32, 16) || wg_s3n_nco(d, g, TB))) {
-      static unsigned long long attr3 = 0ull;
-      if (pmf_first_on_device(&attr3)) {
-        (void)hipFuncSetAttribute((const void*)conv_wgrad_s3_k<TB, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv_wgrad_s3_k<TB, 9>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      }
-      g.x_floats = g.in_rows * g.in_cols * (WS3_XPB / 4);
-      int lds3 = (g.x_floats + WG_ROWS * 32 * 32) * 4;
-      if (lds3 < 16 * 1024) lds3 = 16 * 1024;
-      // (read per launch, not cached: the tests switch variants; a replayed graph never comes here)
-      const char* e_swp = getenv("PMF_WG_SWP");
-      const char* e_w8 = getenv("PMF_WG_W8");
-      const bool swp = !(e_swp && e_swp[0] == '0');
-      const bool small7 = g.in_rows * g.in_cols * 8 <= 256 * 7;
-      const bool w8 = e_w8 && e_w8[0] == '1';
-      const int nco = wg_s3n_nco(d, g, TB);
-      if (nco) {
-        if constexpr (TB > 1) {
-          static unsigned long long attr6 = 0ull;
-          if (pmf_first_on_device(&attr6)) {
-            (void)hipFuncSetAttribute((const void*)conv_wgrad_s3n_k<TB, 7, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)conv_wgrad_s3n_k<TB, 9, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)conv_wgrad_s3n_k<TB, 7, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)conv_wgrad_s3n_k<TB, 9, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)conv_wgrad_s3n_k<TB, 7, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)conv_wgrad_s3n_k<TB, 9, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)conv_wgrad_s3n_k<TB, 7, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)conv_wgrad_s3n_k<TB, 9, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)conv_wgrad_s3n_k<TB, 7, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)conv_wgrad_s3n_k<TB, 9, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)conv_wgrad_s3n_k<TB, 7, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)conv_wgrad_s3n_k<TB, 9, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-          }
-          g.x_floats += WS3_XPB / 4;           // the spare pixel that slots beyond the tile write to
-          int lds6 = 2 * g.x_floats * 4;
-          if (lds6 < 16 * 1024) lds6 = 16 * 1024;
-          const dim3 grid6(d->nsplit, g.nchunks, cdiv(d->Cout, 32 * nco));
-          const bool rag = d->OH % WG_ROWS || d->OW % 32;
-#define S3N_GO(xsl, nc, rg) hipLaunchKernelGGL((conv_wgrad_s3n_k<TB, xsl, nc, rg>), grid6, dim3(256), lds6, s, *d, g)
-#define S3N_PICK(nc) do { if (rag) { if (small7) S3N_GO(7, nc, true); else S3N_GO(9, nc, true); } \
-                          else { if (small7) S3N_GO(7, nc, false); else S3N_GO(9, nc, false); } } while (0)
-          if (nco == 4) S3N_PICK(4);
-          else if (nco == 2) S3N_PICK(2);
-          else S3N_PICK(1);
-#undef S3N_PICK
-#undef S3N_GO
-        }
-      } else
-      // eight waves (the taps of a slab on two waves, two waves per SIMD): 3-10 % faster launch by launch, but 110 KiB
-      // of LDS and 512 threads leave no room for the input-gradient launches the weight gradients run next to:
-      // 16.08 vs 15.97 ms per step -- off unless PMF_WG_W8=1
-      if (swp && w8 && TB > 1) {
-        if constexpr (TB > 1) {
-          static unsigned long long attr5 = 0ull;
-          if (pmf_first_on_device(&attr5)) {
-            (void)hipFuncSetAttribute((const void*)conv_wgrad_s3_w8_k<TB, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)conv_wgrad_s3_w8_k<TB, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-          }
-          g.x_floats += WS3_XPB / 4;           // the spare pixel that slots beyond the tile write to
-          const int lds5 = (2 * g.x_floats + 3 * WG_ROWS * 32 * 32) * 4;
-          if (g.in_rows * g.in_cols * 8 <= 512 * 4) hipLaunchKernelGGL((conv_wgrad_s3_w8_k<TB, 4>), grid, dim3(512), lds5, s, *d, g);
-          else hipLaunchKernelGGL((conv_wgrad_s3_w8_k<TB, 5>), grid, dim3(512), lds5, s, *d, g);
-        }
-      } else if (swp) {      // input tile double-buffered: tile t + 1 is split while tile t is multiplied
-        static unsigned long long attr4 = 0ull;
-        if (pmf_first_on_device(&attr4)) {
-          (void)hipFuncSetAttribute((const void*)conv_wgrad_s3_swp_k<TB, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-          (void)hipFuncSetAttribute((const void*)conv_wgrad_s3_swp_k<TB, 9>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        }
-        g.x_floats += WS3_XPB / 4;           // the spare pixel that slots beyond the tile write to
-        const int lds4 = (2 * g.x_floats + WG_ROWS * 32 * 32) * 4;
-        if (small7) hipLaunchKernelGGL((conv_wgrad_s3_swp_k<TB, 7>), grid, dim3(256), lds4, s, *d, g);
-        else hipLaunchKernelGGL((conv_wgrad_s3_swp_k<TB, 9>), grid, dim3(256), lds4, s, *d, g);
-      } else if (small7) hipLaunchKernelGGL((conv_wgrad_s3_k<TB, 7>), grid, dim3(256), lds3, s, *d, g);
-      else hipLaunchKernelGGL((conv_wgrad_s3_k<TB, 9>), grid, dim3(256), lds3, s, *d, g);
-      piped = true;
-    } else if (wg_simple(d, g, TB, 32) && ((d->cfg >> 8) & 0xff) != 2) {
-      const int lds2 = lds < 16 * 1024 ? 16 * 1024 : lds;   // room for the pixel-group reduction
-      if (g.in_rows * g.in_cols * 8 <= 256 * 7) hipLaunchKernelGGL((conv_wgrad_pipe_k<TB, 1, 7>), grid, dim3(256), lds2, s, *d, g);
-      else hipLaunchKernelGGL((conv_wgrad_pipe_k<TB, 1, 9>), grid, dim3(256), lds2, s, *d, g);
-      piped = true;
-    }
-  }
-  if (!piped) hipLaunchKernelGGL((conv_wgrad_k<TB, NT>), grid, dim3(256), lds, s, *d, g);
+// one launch of instantiation K with the pick's grid / block / LDS.  A kernel may use more than 64 KiB of dynamic LDS only
+// after opting in: done here, once per device and instantiation, when a launch first needs it.
+template <auto K, class... Args>
+static int wg_run(const WgPick& p, const pmf_wgrad_desc_t* d, hipStream_t s, Args... args) {
+  static unsigned long long opted_in = 0ull;
+  if (p.lds > 64 * 1024 && pmf_first_on_device(&opted_in))
+    (void)hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  hipLaunchKernelGGL(K, dim3(d->nsplit, p.gy, p.gz), dim3(p.block), p.lds, s, *d, args...);
   PMF_LAUNCH_CHECK();
-  return (phase & 2) ? wg_reduce(d, g, s) : 0;
+  return 0;
 }
 
-// few-input-channel path (ResNet stem): conditions
-static bool wg_fewc(const pmf_wgrad_desc_t* d) {
-  if (d->nsrc != 1 || d->in_stride != 1 || d->Cin_real > 4 || d->ntaps < 9) return false;
-  if (d->ntaps * d->Cin_real > 160 || d->Cout % 64 || d->OH % WG_ROWS || d->OW % 32) return false;
-  if (d->src[0].flags || d->src[0].scale || d->src[0].cmul) return false;        // raw input only
-  if (d->src[0].H != d->OH || d->src[0].W != d->OW) return false;
-  return true;
-}
-
-static void wg_geometry_fewc(const pmf_wgrad_desc_t* d, WgGeom* g, int* lds) {
-  int l0;
-  wg_geometry(d, 1, 64, g, &l0);
-  int dy_min = 127, dy_max = -127, dx_min = 127, dx_max = -127;
-  for (int t = 0; t < d->ntaps; ++t) {
-    dy_min = d->tdy[t] < dy_min ? d->tdy[t] : dy_min; dy_max = d->tdy[t] > dy_max ? d->tdy[t] : dy_max;
-    dx_min = d->tdx[t] < dx_min ? d->tdx[t] : dx_min; dx_max = d->tdx[t] > dx_max ? d->tdx[t] : dx_max;
+// the pick -> its template instantiation (TB of the tiled families is the template parameter)
+template <int TB>
+static int wg_launch_tiled(const WgPick& p, const pmf_wgrad_desc_t* d, hipStream_t s) {
+#define WG_GO(...) return wg_run<__VA_ARGS__>(p, d, s, p.g)
+#define WG_XSL(k, a, b) do { if (p.XSL == a) WG_GO(k<TB, a>); else WG_GO(k<TB, b>); } while (0)
+#define WG_S3N(nc) do { if (p.RAG) { if (p.XSL == 7) WG_GO(conv_wgrad_s3n_k<TB, 7, nc, true>); else WG_GO(conv_wgrad_s3n_k<TB, 9, nc, true>); } \
+                        else { if (p.XSL == 7) WG_GO(conv_wgrad_s3n_k<TB, 7, nc, false>); else WG_GO(conv_wgrad_s3n_k<TB, 9, nc, false>); } } while (0)
+  switch (p.family) {
+    case WG_UNIT:
+      if (p.NT == 1) WG_GO(conv_wgrad_k<TB, 1>);
+      if (p.NT == 2) WG_GO(conv_wgrad_k<TB, 2>);
+      if constexpr (TB == 1) { if (p.NT == 4) WG_GO(conv_wgrad_k<1, 4>); }
+      break;
+    case WG_PIPE: if (p.XSL == 7) WG_GO(conv_wgrad_pipe_k<TB, 1, 7>); else WG_GO(conv_wgrad_pipe_k<TB, 1, 9>);
+    case WG_STAGED: WG_XSL(conv_wgrad_s3_k, 7, 9);
+    case WG_SWP: WG_XSL(conv_wgrad_s3_swp_k, 7, 9);
+    case WG_W8: if constexpr (TB > 1) WG_XSL(conv_wgrad_s3_w8_k, 4, 5); break;
+    case WG_NSPLIT:
+      if constexpr (TB > 1) { if (p.NCO == 4) WG_S3N(4); else if (p.NCO == 2) WG_S3N(2); else WG_S3N(1); }
+      break;
   }
-  g->in_rows = WG_ROWS + dy_max - dy_min; g->in_cols = 32 + dx_max - dx_min;   // always a halo tile here
-  g->dy_min = dy_min; g->dx_min = dx_min;
-  g->co_tiles = d->Cout / 64; g->tap_batches = 1;
-  const int xfl = (g->in_rows * g->in_cols * d->Cin_real + 4 + 3) & ~3;
-  *lds = (xfl + 2 * 64 * 64) * 4;
-  if (*lds < 16 * 1024) *lds = 16 * 1024;
+#undef WG_S3N
+#undef WG_XSL
+#undef WG_GO
+  return PMF_E_UNSUPPORTED;
 }
 
-static int wg_launch_fewc(const pmf_wgrad_desc_t* d, hipStream_t s, int phase) {
-  WgGeom g;
-  int lds;
-  wg_geometry_fewc(d, &g, &lds);
-  if (!(phase & 1)) return wg_reduce(d, g, s);
-  const int KGn = cdiv(d->ntaps * d->Cin_real, 32);
-  static unsigned long long attr_set = 0ull;
-  if (pmf_first_on_device(&attr_set)) {
-    (void)hipFuncSetAttribute((const void*)wgrad_fewc_k<5>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)wgrad_fewc_k<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)wgrad_fewc_k<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)wgrad_fewc_k<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+static int wg_launch(const WgPick& p, const pmf_wgrad_desc_t* d, hipStream_t s) {
+  const WgGeom& g = p.g;
+  if (p.lds > 160 * 1024) return PMF_E_UNSUPPORTED;
+  switch (p.family) {
+    case WG_FEWC:
+      if (p.KG == 1) return wg_run<wgrad_fewc_k<1>>(p, d, s, g);
+      if (p.KG == 2) return wg_run<wgrad_fewc_k<2>>(p, d, s, g);
+      if (p.KG == 3) return wg_run<wgrad_fewc_k<3>>(p, d, s, g);
+      return wg_run<wgrad_fewc_k<5>>(p, d, s, g);
+    case WG_STREAM: {
+      if (d->nsplit % d->N) return PMF_E_ARG;               // (pmf_conv_wgrad_nsplit: N x S workgroups, one sample each)
+      const int S = d->nsplit / d->N;
+#define WS_CASE(kt, ntl) if (p.KT == kt && p.NTL == ntl) return wg_run<wgrad_stream_k<kt, ntl>>(p, d, s, g.Ktot, g.Cout32, S)
+      WS_CASE(1, 1); WS_CASE(1, 2); WS_CASE(2, 1); WS_CASE(2, 2); WS_CASE(3, 1); WS_CASE(3, 2);
+#undef WS_CASE
+      return PMF_E_UNSUPPORTED;
+    }
+    case WG_DIRECT: case WG_DIRECT_S3:
+      if (((uintptr_t)d->dz & 7) != 0) return PMF_E_ARG;       // float2 loads of dz
+      if (p.family == WG_DIRECT_S3) return wg_run<wgrad_1x1_s3_k>(p, d, s, g.Ktot, g.Cout32);
+      if (p.NCO == 2) return wg_run<wgrad_1x1_k<2>>(p, d, s, g.Ktot, g.Cout32);
+      return wg_run<wgrad_1x1_k<1>>(p, d, s, g.Ktot, g.Cout32);
+    default:
+      if (p.TB == 9) return wg_launch_tiled<9>(p, d, s);
+      if (p.TB == 4) return wg_launch_tiled<4>(p, d, s);
+      return wg_launch_tiled<1>(p, d, s);
   }
-  dim3 grid(d->nsplit, 1, g.co_tiles);
-  if (KGn <= 1) hipLaunchKernelGGL((wgrad_fewc_k<1>), grid, dim3(256), lds, s, *d, g);
-  else if (KGn == 2) hipLaunchKernelGGL((wgrad_fewc_k<2>), grid, dim3(256), lds, s, *d, g);
-  else if (KGn == 3) hipLaunchKernelGGL((wgrad_fewc_k<3>), grid, dim3(256), lds, s, *d, g);
-  else hipLaunchKernelGGL((wgrad_fewc_k<5>), grid, dim3(256), lds, s, *d, g);
-  PMF_LAUNCH_CHECK();
-  return (phase & 2) ? wg_reduce(d, g, s) : 0;
 }
 
-static int wgrad_phases(const pmf_wgrad_desc_t* d, pmf_stream_t st, int phase);
-extern "C" int pmf_conv_wgrad(const pmf_wgrad_desc_t* d, pmf_stream_t st) { return wgrad_phases(d, st, 3); }
-// the two stages separately: the partial-slab kernel, then the deterministic reduction into OIHW (+ bias fold).  A plan
-// runs the reduction on its side stream: nothing downstream needs it before the optimiser (or the gradient all-reduce)
-extern "C" int pmf_conv_wgrad_partial(const pmf_wgrad_desc_t* d, pmf_stream_t st) { return wgrad_phases(d, st, 1); }
-extern "C" int pmf_conv_wgrad_reduce(const pmf_wgrad_desc_t* d, pmf_stream_t st) { return wgrad_phases(d, st, 2); }
-
+// phase 1: the partial-slab kernel; 2: the deterministic reduction into OIHW (+ bias fold); 3: both.  A plan runs the
+// reduction on its side stream: nothing downstream needs it before the optimiser (or the gradient all-reduce)
 static int wgrad_phases(const pmf_wgrad_desc_t* d, pmf_stream_t st, int phase) {
   hipStream_t s = (hipStream_t)st;
   if (!d || d->nsrc < 1 || d->nsrc > PMF_MAX_SRC || d->ntaps < 1 || d->ntaps > PMF_MAX_TAPS || d->nsplit < 1)
     return PMF_E_ARG;
   for (int i = 0; i < d->nsrc; ++i)
     if (d->src[i].C % 8 || d->src[i].ldc % 4) return PMF_E_ARG;
-  if (d->gather && false) return PMF_E_ARG;
-  if (wg_fewc(d)) return wg_launch_fewc(d, s, phase);
-  if (wg_stream(d)) {
-    WgGeom g;
-    int lds;
-    wg_geometry(d, 1, 32, &g, &lds);
-    if (phase & 1) {
-      if (d->nsplit % d->N) return PMF_E_ARG;               // (pmf_conv_wgrad_nsplit: N x S workgroups, one sample each)
-      const int S = d->nsplit / d->N, KT = cdiv(g.Ktot, 32), NTL = g.Cout32 / 32;
-      const dim3 grid(d->nsplit);
-#define WS_CASE(kt, ntl) if (KT == kt && NTL == ntl) hipLaunchKernelGGL((wgrad_stream_k<kt, ntl>), grid, dim3(256), 0, s, *d, g.Ktot, g.Cout32, S)
-      WS_CASE(1, 1); else WS_CASE(1, 2); else WS_CASE(2, 1); else WS_CASE(2, 2); else WS_CASE(3, 1); else WS_CASE(3, 2);
-      else return PMF_E_UNSUPPORTED;
-#undef WS_CASE
-      PMF_LAUNCH_CHECK();
-    }
-    return (phase & 2) ? wg_reduce(d, g, s) : 0;
+  WgPick p;
+  wg_pick(d, &p);
+  if (phase & 1) {
+    const int e = wg_launch(p, d, s);
+    if (e) return e;
   }
-  if (wg_direct_1x1(d)) {
-    WgGeom g;
-    int lds, kb, ob, nco;
-    wg_geometry(d, 1, 32, &g, &lds);
-    if (phase & 1) {
-      if (((uintptr_t)d->dz & 7) != 0) return PMF_E_ARG;       // float2 loads of dz
-      wg_direct_grid(d, &kb, &ob, &nco);
-      static unsigned long long attr_set = 0ull;
-      if (pmf_first_on_device(&attr_set)) {
-        (void)hipFuncSetAttribute((const void*)wgrad_1x1_k<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-        (void)hipFuncSetAttribute((const void*)wgrad_1x1_k<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-      }
-      const dim3 grid(d->nsplit, kb, ob);
-      if (wg_direct_s3(d)) hipLaunchKernelGGL(wgrad_1x1_s3_k, grid, dim3(256), 4 * 16 * 64 * 4, s, *d, g.Ktot, g.Cout32);
-      else if (nco == 2) hipLaunchKernelGGL(wgrad_1x1_k<2>, grid, dim3(256), 8 * 16 * 64 * 4, s, *d, g.Ktot, g.Cout32);
-      else hipLaunchKernelGGL(wgrad_1x1_k<1>, grid, dim3(256), 4 * 16 * 64 * 4, s, *d, g.Ktot, g.Cout32);
-      PMF_LAUNCH_CHECK();
-    }
-    return (phase & 2) ? wg_reduce(d, g, s) : 0;
-  }
-  int TB, NT;
-  wg_config(d, &TB, &NT);
-#define WG_CASE(tb, nt) if (TB == tb && NT == nt) return wg_launch<tb, nt>(d, s, phase)
-  WG_CASE(9, 1); WG_CASE(9, 2);
-  WG_CASE(4, 1); WG_CASE(4, 2);
-  WG_CASE(1, 1); WG_CASE(1, 2); WG_CASE(1, 4);
-#undef WG_CASE
-  return PMF_E_UNSUPPORTED;
+  return (phase & 2) ? wg_reduce(d, p.g, s) : 0;
 }
+extern "C" int pmf_conv_wgrad(const pmf_wgrad_desc_t* d, pmf_stream_t st) { return wgrad_phases(d, st, 3); }
+extern "C" int pmf_conv_wgrad_partial(const pmf_wgrad_desc_t* d, pmf_stream_t st) { return wgrad_phases(d, st, 1); }
+extern "C" int pmf_conv_wgrad_reduce(const pmf_wgrad_desc_t* d, pmf_stream_t st) { return wgrad_phases(d, st, 2); }

@@ -27,9 +27,9 @@ def _err(a, b):
 class Harness:
     """inputs -> graph(P, views) -> outputs; runs fwd+bwd on the GPU and the same function in float64 autograd."""
 
-    def __init__(self, shapes, needs_grad=None, masks=0):
-        self.P = Plan(torch.device(DEV), True)
-        self.P.masks = torch.ones(max(masks, 4), device=DEV)
+    def __init__(self, shapes, needs_grad=None, masks=0, dev=DEV):
+        self.P = Plan(torch.device(dev), True)
+        self.P.masks = torch.ones(max(masks, 4), device=dev)
         self.shapes = shapes
         self.inputs = []
         for i, (n, c, h, w) in enumerate(shapes):
@@ -192,8 +192,11 @@ def test_conv_unit_splitk_two_launch_form(name, monkeypatch):
         _conv_case(next(c for c in CONVS if c[0] == name), 32 | (1 << 8) | (ks << 16))
 
 
-@pytest.mark.parametrize("env", [{"PMF_WG_SWP": "0"}, {"PMF_WG_W8": "1"}, {"PMF_WG_S3N": "0"}, {"PMF_WG_S3N": "2"}],
-                         ids=["staged", "eight_waves", "swp_pixel_split", "nsplit_two_tiles"])
+WGRAD_VARIANT_ENVS = {"staged": {"PMF_WG_SWP": "0"}, "eight_waves": {"PMF_WG_W8": "1"}, "swp_pixel_split": {"PMF_WG_S3N": "0"},
+                      "nsplit_two_tiles": {"PMF_WG_S3N": "2"}}
+
+
+@pytest.mark.parametrize("env", list(WGRAD_VARIANT_ENVS.values()), ids=list(WGRAD_VARIANT_ENVS))
 def test_conv_unit_wgrad_variants(env, monkeypatch):
     """the split-bf16 weight-gradient kernel's other forms (conv_wgrad.hip): the two-barrier staged loop that the
     software-pipelined form replaced (PMF_WG_SWP=0), the 512-thread form with the taps of a slab on two waves
@@ -246,7 +249,9 @@ def test_conv_unit_direct_1x1(case, monkeypatch):
     _conv_case(case, 64 | (2 << 8) | (1 << 16))
 
 
-def _conv_case(case, cfg):
+def _conv_graph(case, dev=DEV):
+    """the plan of one CONVS entry (a conv over its operand views, + activation / BatchNorm) on ``dev``; also what
+    tests/test_wgrad_dispatch_host.py builds -- on the CPU, never run -- to read the weight-gradient descriptor"""
     name, N, H, W, cins, Cout, k, dil, pad, stride, bias, mode, use_bn = case
     conv = nn.Conv2d(sum(cins), Cout, k, stride, pad, dil, bias=bias)
     bn = nn.BatchNorm2d(Cout) if use_bn else None
@@ -258,11 +263,8 @@ def _conv_case(case, cfg):
             bn.weight.copy_(det_tensor(name + ".g", (Cout,), 0.5, 1.5))
             bn.bias.copy_(det_tensor(name + ".be", (Cout,), -0.5, 0.5))
     conv_d, bn_d = conv, bn
-    conv, bn = conv.to(DEV), (bn.to(DEV) if bn is not None else None)
-    import copy
-    conv64 = copy.deepcopy(conv_d).cpu().double()
-    bn64 = copy.deepcopy(bn_d).cpu().double().train() if bn_d is not None else None
-    Hn = Harness([(N, c, H, W) for c in cins], masks=N * sum(cins))
+    conv, bn = conv.to(dev), (bn.to(dev) if bn is not None else None)
+    Hn = Harness([(N, c, H, W) for c in cins], masks=N * sum(cins), dev=dev)
     P = Hn.P
     # a Dropout2d multiplier on the 2nd operand when there are several
     cm = None
@@ -271,7 +273,7 @@ def _conv_case(case, cfg):
         v = V(t)
         if i == 1:
             cm = (det_tensor(name + ".cm", (N, cins[1])) > -0.5).float() * 1.25
-            P.masks[:N * cins[1]].copy_(cm.reshape(-1).to(DEV))
+            P.masks[:N * cins[1]].copy_(cm.reshape(-1).to(dev))
             v = v.with_cmul(0, cins[1])
         views.append(v)
     if mode == "act_bn":
@@ -284,6 +286,15 @@ def _conv_case(case, cfg):
         out = P.conv(views, conv, L.ACT_NONE, bn, "bn_act", True, name="u")
     else:
         out = P.conv(views, conv, L.ACT_NONE, bn, "bn_act", False, name="u")
+    return Hn, out, conv_d, bn_d, conv, bn, cm
+
+
+def _conv_case(case, cfg):
+    name, N, H, W, cins, Cout, k, dil, pad, stride, bias, mode, use_bn = case
+    Hn, out, conv_d, bn_d, conv, bn, cm = _conv_graph(case)
+    import copy
+    conv64 = copy.deepcopy(conv_d).cpu().double()
+    bn64 = copy.deepcopy(bn_d).cpu().double().train() if bn_d is not None else None
     xs = [det_tensor("%s.x%d" % (name, i), s) for i, s in enumerate(Hn.shapes)]
     OH = (H + 2 * pad - dil * (k - 1) - 1) // stride + 1
     OW = (W + 2 * pad - dil * (k - 1) - 1) // stride + 1

@@ -34,6 +34,21 @@ CASES = [  # name, N, H, W, Cin, Cout, k, dil
     ("32nd_2048_512_1x1", 2, 2, 64, 2048, 512, 1, 1),
     ("32nd_512_2048_1x1", 2, 2, 64, 512, 2048, 1, 1),
 ]
+def wgrad_desc(case, x=0, dz=0, s3=True):
+    """weight-gradient descriptor of a CASES entry over the device pointers x / dz (0: shape only, for host-side queries);
+    nsplit is left at 1 for pmf_conv_wgrad_nsplit"""
+    name, N, H, W, ci, co, k, dil = case
+    taps = G.taps_of(k, k, dil, 1 if k == 2 else dil * (k - 1) // 2)
+    wd = L.WgradDesc()
+    wd.N, wd.OH, wd.OW, wd.Cout, wd.nsrc = N, H, W, co, 1
+    wd.src[0].x, wd.src[0].C, wd.src[0].ldc, wd.src[0].H, wd.src[0].W = x, ci, ci, H, W
+    wd.ntaps = len(taps)
+    for i, (dy, dx) in enumerate(taps): wd.tdy[i], wd.tdx[i], wd.tap_widx[i] = dy, dx, i
+    wd.in_stride = 1; wd.dz, wd.dz_ldc = dz, co
+    wd.flags = L.WGRAD_S3 if s3 else 0              # split-bf16 kernels (the plan's default)
+    wd.Cin_real, wd.KHW = ci, k * k                 # (before the split count: the few-channel stem kernel keys on it)
+    wd.nsplit = 1
+    return wd
 def timeit(fn, n=200):
     # the shader clock needs tens of milliseconds of load to ramp from idle: warm up long enough, then time
     for _ in range(400): fn()
@@ -86,18 +101,11 @@ def run(which, filt):
                     name, cfg, res[0], gf / res[0] * 1e3, res[1], gf / res[1] * 1e3), flush=True)
         if which in ("wgrad", "all"):
             dz = torch.randn(N, H, W, co, device="cuda")
-            wd = L.WgradDesc()
-            wd.N, wd.OH, wd.OW, wd.Cout, wd.nsrc = N, H, W, co, 1
-            wd.src[0].x, wd.src[0].C, wd.src[0].ldc, wd.src[0].H, wd.src[0].W = x.data_ptr(), ci, ci, H, W
-            wd.ntaps = len(taps)
-            for i, (dy, dx) in enumerate(taps): wd.tdy[i], wd.tdx[i], wd.tap_widx[i] = dy, dx, i
-            wd.in_stride = 1; wd.dz, wd.dz_ldc = dz.data_ptr(), co
-            wd.flags = L.WGRAD_S3 if os.environ.get("WG_S3", "1") != "0" else 0     # split-bf16 kernels (the plan's default)
-            wd.Cin_real, wd.KHW = ci, k * k          # (before the split count: the few-channel stem kernel keys on it)
-            wd.nsplit = 1; wd.nsplit = lib.pmf_conv_wgrad_nsplit(C.byref(wd))
+            wd = wgrad_desc((name, N, H, W, ci, co, k, dil), x.data_ptr(), dz.data_ptr(), os.environ.get("WG_S3", "1") != "0")
+            wd.nsplit = lib.pmf_conv_wgrad_nsplit(C.byref(wd))
             part = torch.empty(lib.pmf_conv_wgrad_workspace(C.byref(wd)), dtype=torch.uint8, device="cuda")
             gw = torch.empty(co, ci, k, k, device="cuda")
-            wd.partial, wd.dw_oihw, wd.Cin_real, wd.KHW = part.data_ptr(), gw.data_ptr(), ci, k * k
+            wd.partial, wd.dw_oihw = part.data_ptr(), gw.data_ptr()
             st = G.stream()
             us = timeit(lambda: lib.pmf_conv_wgrad(C.byref(wd), st))
             print("wgrad %-22s %8.1f us  %6.1f TF/s  (nsplit %d)" % (name, us, gf / us * 1e3, wd.nsplit), flush=True)

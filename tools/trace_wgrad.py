@@ -9,7 +9,7 @@ sys.path.insert(0, ROOT)
 import numpy as np, torch
 from pmf_amd import _lib as L
 from tests import gpu_helpers as G
-from tools.bench_conv import CASES
+from tools.bench_conv import CASES, wgrad_desc
 
 def build():
     so = "/tmp/libpmf_wg_trace.so"
@@ -25,22 +25,12 @@ def main(filt, ns):
     lib = L.lib()
     for name, N, H, W, ci, co, k, dil in CASES:
         if filt and filt not in name: continue
-        pad = dil * (k - 1) // 2
-        if k == 2: pad = 1
         x = torch.randn(N, H, W, ci, device="cuda"); dz = torch.randn(N, H, W, co, device="cuda")
-        taps = G.taps_of(k, k, dil, pad)
-        wd = L.WgradDesc()
-        wd.N, wd.OH, wd.OW, wd.Cout, wd.nsrc = N, H, W, co, 1
-        wd.src[0].x, wd.src[0].C, wd.src[0].ldc, wd.src[0].H, wd.src[0].W = x.data_ptr(), ci, ci, H, W
-        wd.ntaps = len(taps)
-        for i, (dy, dx) in enumerate(taps): wd.tdy[i], wd.tdx[i], wd.tap_widx[i] = dy, dx, i
-        wd.in_stride = 1; wd.dz, wd.dz_ldc = dz.data_ptr(), co
-        wd.flags = L.WGRAD_S3
-        wd.Cin_real, wd.KHW = ci, k * k
-        wd.nsplit = 1; wd.nsplit = ns if ns else lib.pmf_conv_wgrad_nsplit(C.byref(wd))
+        wd = wgrad_desc((name, N, H, W, ci, co, k, dil), x.data_ptr(), dz.data_ptr())
+        wd.nsplit = ns if ns else lib.pmf_conv_wgrad_nsplit(C.byref(wd))
         part = torch.empty(lib.pmf_conv_wgrad_workspace(C.byref(wd)), dtype=torch.uint8, device="cuda")
         gw = torch.empty(co, ci, k, k, device="cuda")
-        wd.partial, wd.dw_oihw, wd.Cin_real, wd.KHW = part.data_ptr(), gw.data_ptr(), ci, k * k
+        wd.partial, wd.dw_oihw = part.data_ptr(), gw.data_ptr()
         st = G.stream()
         for _ in range(300): tl.pmf_conv_wgrad(C.byref(wd), st)
         torch.cuda.synchronize()
@@ -58,14 +48,14 @@ def main(filt, ns):
         print("== %s nsplit %d: %d workgroups, %d stamps, launch span %d ticks; per-workgroup total median %d" % (
             name, wd.nsplit, len(t), cnt, span, int(np.median(t[:, cnt - 1] - t[:, 0]))))
         names = ["prologue"]
-        per = ["X barrier", "split+store X", "Y barrier", "fetch + dz wait + B prep", "108 MFMAs"]
-        if os.environ.get("PMF_WG_S3N", "4") not in ("0", "1") and co % 64 == 0 and os.environ.get("PMF_WG_SWP", "1") != "0" \
-                and os.environ.get("PMF_WG_W8", "0") != "1":
-            per = ["barrier + loads landed", "MFMAs + split(t+1) + dz prep", "fetch(t+2)"]     # N-split body: three stamps per tile
-        elif os.environ.get("PMF_WG_SWP", "1") != "0":     # software-pipelined body: three stamps per tile
-            per = ["barrier", "dz wait + B prep", "108 MFMAs + split(t+1)", "fetch(t+2)"]
-            if os.environ.get("PMF_WG_W8", "0") == "1":
-                per = ["barrier", "dz DMA + input wait", "MFMAs + split(t+1) + fetch(t+2) + B prep(t+1)", "dz wait"]
+        # stamps per tile of the body that ran (the library's own selection, same PMF_WG_* environment as the traced copy)
+        variant = lib.pmf_conv_wgrad_variant(C.byref(wd))
+        per = {L.WG_STAGED: ["X barrier", "split+store X", "Y barrier", "fetch + dz wait + B prep", "108 MFMAs"],
+               L.WG_NSPLIT: ["barrier + loads landed", "MFMAs + split(t+1) + dz prep", "fetch(t+2)"],
+               L.WG_SWP: ["barrier", "dz wait + B prep", "108 MFMAs + split(t+1)", "fetch(t+2)"],
+               L.WG_W8: ["barrier", "dz DMA + input wait", "MFMAs + split(t+1) + fetch(t+2) + B prep(t+1)", "dz wait"]}.get(variant)
+        if per is None:
+            print("== %s: variant %d is not a split-bf16 tiled kernel, no stamps" % (name, variant)); continue
         ntile = (cnt - 1 - 1 - 2) // len(per)
         for i in range(ntile): names += ["t%d %s" % (i, p) for p in per]
         names += ["loop exit", "reduce+write"]
