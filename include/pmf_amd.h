@@ -621,6 +621,30 @@ int pmf_eval_points(const float* prob, int32_t C, int32_t H, int32_t W, int32_t 
                     const float* inv_gauss, float cutoff, int64_t* knn_ws, const int32_t* sem, const int32_t* src_idx,
                     const int32_t* lut, int32_t nlut, int64_t* conf, const int32_t* lut_inv, int32_t nlut_inv,
                     int32_t* labels, uint32_t* labels_inv, pmf_stream_t s);
+/* ---- EPMF evaluation on nuScenes: six views per sweep, merged on the device (tasks/epmf_eval_nuscenes/infer.py) --------
+ * Views are padded to multiples of 64 with the rows at the bottom only: window origin (top = 0, left = (W - w) / 2).
+ * State per sweep, owned by the caller: conf_full f32[P], label_full int32[P], both zero before the first view.
+ * pmf_eval_view_merge: one view.  For each of the K kept points at box-relative pixel (x_data[k] - x_min, y_data[k] - y_min)
+ * of the prob f32[C,H,W] window: argmax == NULL (gather): conf = max_c prob, label = first class attaining it (torch.max
+ * over dim 0: a NaN is the maximum; a point outside the window gives (0, 0)).  argmax != NULL (KNN): label = the vote of
+ * pmf_knn_vote on that int32[h,w] map (proj_range f32[h,w], unproj_range f32[K]); conf = the SAME vote over the window's
+ * int32-truncated confidence map, cast to float -- the reference passes its float confidence map through a module that
+ * casts to integer, a quirk kept for equal labels (gather is the reference's default).  KNN workspaces: knn_ws
+ * int64[4K + 2], conf_ws int32[h * w].  Merge: p = src_idx[k] (0 <= p < P, others skipped); if conf_full[p] < conf (strict:
+ * an earlier view wins ties, NaN never wins) then conf_full[p] = conf, label_full[p] = label.  src_idx must not repeat
+ * inside one view and the views of a sweep must be issued in order on one stream: the kernel uses no atomics.
+ * C <= 64.  K == 0 is a no-op. */
+int pmf_eval_view_merge(const float* prob, int32_t C, int32_t H, int32_t W, int32_t top, int32_t left, int32_t h, int32_t w,
+                        const int32_t* x_data, const int32_t* y_data, int32_t x_min, int32_t y_min, int64_t K,
+                        const int32_t* src_idx, int64_t P, const int32_t* argmax, const float* proj_range,
+                        const float* unproj_range, int32_t knn, int32_t search, const float* inv_gauss, float cutoff,
+                        int64_t* knn_ws, int32_t* conf_ws, float* conf_full, int32_t* label_full, pmf_stream_t s);
+/* pmf_eval_sweep_finish: after the last view, for every point p < P: pred = label_full[p]; conf (optional, int64[C][C],
+ * C <= 64) += (pred, gt) with gt = pred != 0 ? lut[sem[p]] : 0 (sem int32[P] raw ids, ids outside the lut -> class 0;
+ * points no camera labelled land in the ignored cell [0][0]); out_u8 (optional) uint8[P] = pred; then conf_full[p] = 0,
+ * label_full[p] = 0 for the next sweep.  P == 0 is a no-op. */
+int pmf_eval_sweep_finish(float* conf_full, int32_t* label_full, int64_t P, const int32_t* sem, const int32_t* lut,
+                          int32_t nlut, int32_t C, int64_t* conf, uint8_t* out_u8, pmf_stream_t s);
 /* pixel splits pmf_conv_wgrad will use for this descriptor (sizes `partial`) */
 int pmf_conv_wgrad_nsplit(const pmf_wgrad_desc_t* d);
 /* the kernel family pmf_conv_wgrad runs for this descriptor under the current PMF_WG_* switches (the same selection that

@@ -219,3 +219,130 @@ extern "C" int pmf_eval_points(const float* prob, int32_t C, int32_t H, int32_t 
   PMF_LAUNCH_CHECK();
   return 0;
 }
+
+// ---- (d) nuScenes: six views per sweep, merged on the device as they arrive ----------------------------------------------
+// (tasks/epmf_eval_nuscenes/infer.py of the reference: a running (confidence, label) pair per LiDAR point of the sweep; a
+// later view overwrites a point only where it is STRICTLY more confident; after the sixth view the points some camera
+// labelled non-zero are scored.)  The state conf_full f32[P] / label_full int32[P] lives on the device, zero at the start of
+// a sweep; pmf_eval_sweep_finish zeroes it again.
+//
+// KNN mode: the reference sends the float confidence map through the same KNN module as the argmax map, and that module
+// casts its map to int64 -- so the "confidence" that enters the merge is the vote over trunc(confidence), an integer
+// class id cast back to float (1.0 for practically every point of a softmax map: the first view that sees a point keeps
+// it).  That is a quirk of the reference, reproduced here so labels agree in both modes; gather mode is its default.
+__global__ __launch_bounds__(256) void eval_conf_trunc_k(const float* __restrict__ prob, int C, int H, int W, int top,
+                                                         int left, int h, int w, int32_t* __restrict__ cmap) {
+  const int64_t HW = (int64_t)H * W, hw = (int64_t)h * w;
+  for (int64_t o = blockIdx.x * (int64_t)256 + threadIdx.x; o < hw; o += (int64_t)gridDim.x * 256) {
+    const int r = (int)(o / w), c = (int)(o - (int64_t)r * w);
+    const float* p = prob + (int64_t)(top + r) * W + left + c;
+    float best = 0.f;
+    int bi = 0;
+    for (int j = 0; j < C; ++j) ev_take(p[(int64_t)j * HW], j, best, bi);
+    cmap[o] = (best == best && fabsf(best) < 2.0e9f) ? (int)best : 0;        // .long(): towards zero; NaN -> no class
+  }
+}
+
+// One lane per kept point of the view: coalesced x / y / src (and vote) reads, C strided plane reads at its pixel.
+// No atomics: inside one view src has no duplicates (every kept point is one point of the sweep), and the views of a
+// sweep are launched on one stream in order, so each (conf_full[p], label_full[p]) pair has a single writer at a time.
+__global__ __launch_bounds__(256) void eval_view_merge_k(const float* __restrict__ prob, int C, int H, int W, int top,
+                                                         int left, int h, int w, const int32_t* __restrict__ xd,
+                                                         const int32_t* __restrict__ yd, int x_min, int y_min, int64_t K,
+                                                         const int32_t* __restrict__ src, int64_t P,
+                                                         const int64_t* __restrict__ vlab, const int64_t* __restrict__ vconf,
+                                                         float* __restrict__ conf_full, int32_t* __restrict__ label_full) {
+  const int64_t HW = (int64_t)H * W;
+  const int64_t k = blockIdx.x * (int64_t)256 + threadIdx.x;
+  if (k >= K) return;
+  float conf = 0.f;
+  int pred = 0;
+  if (vlab) {
+    pred = (int)vlab[k];
+    conf = (float)vconf[k];
+  } else {
+    const int r = xd[k] - x_min, c = yd[k] - y_min;
+    if (r >= 0 && r < h && c >= 0 && c < w) {
+      const float* p = prob + (int64_t)(top + r) * W + left + c;
+      for (int j = 0; j < C; ++j) ev_take(p[(int64_t)j * HW], j, conf, pred);   // pred_output[0].max(dim=0)
+    }
+  }
+  const int64_t p = src[k];
+  if (p < 0 || p >= P) return;
+  if (conf_full[p] < conf) {          // strict: the earlier view wins a tie, a NaN confidence never wins
+    conf_full[p] = conf;
+    label_full[p] = pred;
+  }
+}
+
+extern "C" int pmf_eval_view_merge(const float* prob, int32_t C, int32_t H, int32_t W, int32_t top, int32_t left, int32_t h,
+                                   int32_t w, const int32_t* x_data, const int32_t* y_data, int32_t x_min, int32_t y_min,
+                                   int64_t K, const int32_t* src_idx, int64_t P, const int32_t* argmax,
+                                   const float* proj_range, const float* unproj_range, int32_t knn, int32_t search,
+                                   const float* inv_gauss, float cutoff, int64_t* knn_ws, int32_t* conf_ws,
+                                   float* conf_full, int32_t* label_full, pmf_stream_t s) {
+  if (!ev_window_ok(C, H, W, top, left, h, w) || K < 0 || P < 0 || C > EV_MAXC) return PMF_E_ARG;
+  if (K == 0) return 0;
+  if (!prob || !x_data || !y_data || !src_idx || !conf_full || !label_full) return PMF_E_ARG;
+  hipStream_t st = (hipStream_t)s;
+  const int64_t *vlab = nullptr, *vconf = nullptr;
+  if (argmax) {                                   // KNN: ws = px[K] | py[K] | offsets[2] | labels[K] | confidences[K]
+    if (!proj_range || !unproj_range || !inv_gauss || !knn_ws || !conf_ws) return PMF_E_ARG;
+    int64_t *px = knn_ws, *py = knn_ws + K, *off = knn_ws + 2 * K, *lab = knn_ws + 2 * K + 2, *cf = knn_ws + 3 * K + 2;
+    hipLaunchKernelGGL(eval_knn_prep_k, dim3((unsigned)cdiv64(K, 256)), dim3(256), 0, st, x_data, y_data, x_min, y_min, K,
+                       px, py, off);
+    const int64_t g = cdiv64((int64_t)h * w, 256);
+    hipLaunchKernelGGL(eval_conf_trunc_k, dim3((unsigned)(g < 2048 ? g : 2048)), dim3(256), 0, st, prob, C, H, W, top, left,
+                       h, w, conf_ws);
+    PMF_LAUNCH_CHECK();
+    int rc = knn_vote_batch_impl(proj_range, unproj_range, nullptr, argmax, px, py, off, 1, h, w, K, knn, search, inv_gauss,
+                                 cutoff, C, lab, s);
+    if (rc != 0) return rc;
+    rc = knn_vote_batch_impl(proj_range, unproj_range, nullptr, conf_ws, px, py, off, 1, h, w, K, knn, search, inv_gauss,
+                             cutoff, C, cf, s);
+    if (rc != 0) return rc;
+    vlab = lab;
+    vconf = cf;
+  }
+  hipLaunchKernelGGL(eval_view_merge_k, dim3((unsigned)cdiv64(K, 256)), dim3(256), 0, st, prob, C, H, W, top, left, h, w,
+                     x_data, y_data, x_min, y_min, K, src_idx, P, vlab, vconf, conf_full, label_full);
+  PMF_LAUNCH_CHECK();
+  return 0;
+}
+
+// One lane per point of the sweep: the merged label, the (pred, gt) count over the points some camera labelled non-zero
+// (gt = lut[sem] * (pred != 0): the others land in the ignored cell [0][0]), the uint8 label, and the state back to zero.
+__global__ __launch_bounds__(256) void eval_sweep_finish_k(float* __restrict__ conf_full, int32_t* __restrict__ label_full,
+                                                           int64_t P, const int32_t* __restrict__ sem,
+                                                           const int32_t* __restrict__ lut, int nlut, int C,
+                                                           unsigned long long* __restrict__ conf,
+                                                           uint8_t* __restrict__ out_u8) {
+  __shared__ unsigned hist[EV_MAXC * EV_MAXC];
+  if (conf) ev_hist_zero(hist, C);
+  for (int64_t p = blockIdx.x * (int64_t)256 + threadIdx.x; p < P; p += (int64_t)gridDim.x * 256) {
+    const int pred = label_full[p];
+    if (conf) {
+      const int sl = sem[p];
+      const int t = (pred != 0 && sl >= 0 && sl < nlut) ? lut[sl] : 0;
+      if (t >= 0 && t < C && pred >= 0 && pred < C) atomicAdd(&hist[pred * C + t], 1u);
+    }
+    if (out_u8) out_u8[p] = (uint8_t)pred;
+    conf_full[p] = 0.f;
+    label_full[p] = 0;
+  }
+  if (conf) ev_hist_flush(hist, C, conf);
+}
+
+extern "C" int pmf_eval_sweep_finish(float* conf_full, int32_t* label_full, int64_t P, const int32_t* sem,
+                                     const int32_t* lut, int32_t nlut, int32_t C, int64_t* conf, uint8_t* out_u8,
+                                     pmf_stream_t s) {
+  if (P < 0 || C < 1 || C > EV_MAXC) return PMF_E_ARG;
+  if (P == 0) return 0;
+  if (!conf_full || !label_full) return PMF_E_ARG;
+  if (conf && (!sem || !lut || nlut < 1)) return PMF_E_ARG;
+  const int64_t g = cdiv64(P, 256);
+  hipLaunchKernelGGL(eval_sweep_finish_k, dim3((unsigned)(g < EV_GRID ? g : EV_GRID)), dim3(256), 0, (hipStream_t)s,
+                     conf_full, label_full, P, sem, lut, nlut, C, (unsigned long long*)conf, out_u8);
+  PMF_LAUNCH_CHECK();
+  return 0;
+}

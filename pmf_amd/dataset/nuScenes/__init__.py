@@ -17,3 +17,19 @@ class Nuscenes(object):
         raise NotImplementedError("nuScenes table reader: install nuscenes-devkit and plug a dataset object with "
                                   "loadDataByIndex / loadImage / parsePathInfoByIndex / proj_matrix / class_map_lut "
                                   "into PerspectiveViewLoader (INTEGRATION.md)")
+
+
+class NuscenesV2(object):
+    """pc_processor/dataset/nuScenes/dataset_nuscenes_v2.py (the EPMF reader: mapLidar2CameraCropYaw, per-camera yaw
+    windows): the same devkit dependency as Nuscenes.  PerspectiveViewLoaderV2 and tasks/epmf_eval_nuscenes take any
+    object with its attributes."""
+
+    def __init__(self, root, version="v1.0-trainval", split="train", **kw):
+        try:
+            import nuscenes  # noqa: F401
+        except ImportError as e:
+            raise ImportError("pc_processor.dataset.nuScenes.NuscenesV2 needs the nuscenes-devkit package (pip install "
+                              "nuscenes-devkit), which is not installed in this environment") from e
+        raise NotImplementedError("nuScenes table reader: install nuscenes-devkit and plug a dataset object with "
+                                  "loadDataByIndex / loadImage / parsePathInfoByIndex / mapLidar2CameraCropYaw / "
+                                  "labelMapping / token_list into PerspectiveViewLoaderV2 (INTEGRATION.md)")

@@ -10,7 +10,12 @@ Training path (:25-34,50-57,142-153): random image rescale in [1, 1.2] (numpy RN
 as in the reference), coordinates scaled with it inside the projection kernel, bottom / centred horizontal zero padding
 to (proj_ht, proj_wt), then flip / rotate(15) / crop as one HIP gather (FlipRotateCrop).  img_aug (:19-23,46-47,
 ColorJitter(*PVconfig.img_jitter) before the rescale) runs on the device (perspective_view_loader.ColorJitter ->
-pmf_color_jitter, bit-exact Pillow arithmetic); the jittered uint8 frame comes back once for the host-side PIL resize."""
+pmf_color_jitter, bit-exact Pillow arithmetic); the jittered uint8 frame comes back once for the host-side PIL resize.
+A ``NuscenesV2``-type dataset -- one with ``mapLidar2CameraCropYaw(seq_id, pointcloud) -> (camera-frame rows f[K, >=4],
+(row, col) f64[K,2], keep bool[P])`` and no ``proj_matrix`` -- keeps its geometry on the host (the devkit's chain of rigid
+transforms, dataset_nuscenes_v2.py:301-375); what the loader does with the result (:72-141: truncation, bounding box, depth
+of the camera-frame points, last-writer-wins scatter, labelMapping as a 256-entry table, RGB window) is one packed upload +
+pmf_project_v2_scatter.  Validation only: the training path on such a dataset is not implemented."""
 import ctypes as C
 import math
 
@@ -87,8 +92,76 @@ class PerspectiveViewLoaderV2(Dataset):
         if is_train:                      # :25-34 flip / rotate(15) / crop to (proj_ht, proj_wt) as one HIP gather
             from .perspective_view_loader import FlipRotateCrop
             self.aug_ops = FlipRotateCrop(self.pv_config["proj_ht"], self.pv_config["proj_wt"])
+        self._nus_lut = self._ident = None            # NuscenesV2-type datasets: label table, identity source indices
+
+    def _is_nus_v2(self):
+        return hasattr(self.dataset, "mapLidar2CameraCropYaw") and not hasattr(self.dataset, "proj_matrix")
+
+    def _nus_label_lut(self):
+        """dataset.labelMapping (np.vectorize over a dictionary) as a 256-entry table, as NusPerspectiveViewLoader"""
+        if self._nus_lut is None:
+            keys = sorted(self.dataset.map_name_from_general_index_to_segmentation_index.keys())
+            lut = np.zeros(256, np.int32)
+            lut[keys] = self.dataset.labelMapping(np.asarray(keys, np.uint8)[:, None])
+            self._nus_lut = torch.from_numpy(lut).to(self.device)
+        return self._nus_lut
+
+    def _nus_item(self, index):
+        """one camera view of a NuscenesV2-type dataset -> (proj, xy_index, depth, keep, extra, pointcloud)"""
+        if self.is_train:
+            raise NotImplementedError("PerspectiveViewLoaderV2: training (is_train=True) on a NuscenesV2-type dataset "
+                                      "(mapLidar2CameraCropYaw, no proj_matrix) is not implemented; use is_train=False")
+        dev = torch.device(self.device)
+        if dev.type != "cuda":
+            raise RuntimeError("PerspectiveViewLoaderV2 runs on the GPU only (device=%s)" % self.device)
+        from .perspective_view_loader import image_to_device, upload_packed
+        image = self.dataset.loadImage(index)
+        img_dev = None
+        if self.img_jitter is not None:
+            img_dev = self.img_jitter(image_to_device(image, dev))
+        pointcloud, sem_label, _ = self.dataset.loadDataByIndex(index)
+        seq_id, _ = self.dataset.parsePathInfoByIndex(index)
+        crop, xy_index, keep_mask = self.dataset.mapLidar2CameraCropYaw(seq_id, pointcloud)
+        xy_index = np.ascontiguousarray(xy_index, np.float64)
+        keep_mask = np.asarray(keep_mask, np.bool_)
+        K = int(xy_index.shape[0])
+        if K == 0:
+            raise ValueError("PerspectiveViewLoaderV2: no point inside the camera's field of view")
+        x_data = np.ascontiguousarray(xy_index[:, 0].astype(np.int32))
+        y_data = np.ascontiguousarray(xy_index[:, 1].astype(np.int32))
+        x_min, x_max, y_min, y_max = int(x_data.min()), int(x_data.max()), int(y_data.min()), int(y_data.max())
+        h, w = x_max - x_min + 1, y_max - y_min + 1
+        # depth of the CAMERA-frame points, in the precision the dataset hands them over (:97); it is one of the scatter's
+        # inputs and the coordinates are host arrays, so it is taken here and travels with the packed upload
+        depth = np.linalg.norm(crop[:, :3], 2, axis=1).astype(np.float32)
+        sem_raw = np.ascontiguousarray(sem_label).reshape(-1).astype(np.int32)
+        parts = [np.ascontiguousarray(crop[:, :4], np.float32), sem_raw[keep_mask], x_data, y_data, depth,
+                 np.flatnonzero(keep_mask).astype(np.int32), sem_raw, xy_index, keep_mask.view(np.uint8)]
+        if img_dev is None:
+            parts.append(np.ascontiguousarray(np.asarray(image), np.uint8))
+        up = upload_packed(parts, dev)                       # one host -> device copy per view
+        pts, sem_kept, xd, yd, dep, src, sem, xy, keep = up[:9]
+        img = img_dev if img_dev is not None else up[9]
+        if self._ident is None or self._ident.shape[0] < K:  # row k of the cropped cloud is its own source
+            self._ident = torch.arange(max(K, 1 << 16), dtype=torch.int32, device=dev)
+        lut = self._nus_label_lut()
+        out = torch.empty((10, h, w), dtype=torch.float32, device=dev)
+        pix = torch.empty(h * w, dtype=torch.int32, device=dev)
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        L.check(L.lib().pmf_project_v2_scatter(pts.data_ptr(), sem_kept.data_ptr(), self._ident.data_ptr(), xd.data_ptr(),
+                                               yd.data_ptr(), dep.data_ptr(), K, img.data_ptr(), img.shape[0], img.shape[1],
+                                               lut.data_ptr(), lut.shape[0], x_min, y_min, h, w, out.data_ptr(),
+                                               pix.data_ptr(), st), "pmf_project_v2_scatter")
+        extra = dict(x_data=xd, y_data=yd, src=src, sem=sem, lut=lut, x_min=x_min, y_min=y_min)
+        return out, xy, dep, keep.bool(), extra, pointcloud
 
     def __getitem__(self, index):
+        if self._is_nus_v2():
+            proj, xy, depth, keep, _, pointcloud = self._nus_item(index)
+            if not self.return_uproj:
+                raise NotImplementedError("PerspectiveViewLoaderV2 on a NuscenesV2-type dataset serves the evaluation "
+                                          "layout only (return_uproj=True, is_train=False)")
+            return proj, xy, depth, keep, torch.as_tensor(np.asarray(pointcloud))
         image = self.dataset.loadImage(index)
         if self.img_jitter is not None:
             from .perspective_view_loader import image_to_device
@@ -133,7 +206,10 @@ class PerspectiveViewLoaderV2(Dataset):
 
     def _eval_item(self, index):
         """validation frame for the evaluation task (return_uproj layout): (proj, xy_index, depth, keep, extra) with
-        ``extra`` the device tensors of _project_frame_v2; the public return tuple of __getitem__ is unchanged."""
+        ``extra`` the device tensors of _project_frame_v2; the public return tuple of __getitem__ is unchanged.  On a
+        NuscenesV2-type dataset ``src`` is the position of each kept point in the sweep and ``sem`` the sweep's raw labels."""
+        if self._is_nus_v2():
+            return self._nus_item(index)[:5]
         image = self.dataset.loadImage(index)
         if self.img_jitter is not None:
             from .perspective_view_loader import image_to_device

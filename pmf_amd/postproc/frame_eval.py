@@ -8,6 +8,13 @@ Here that is three HIP passes (csrc/eval.hip):
   pixels  argmax over the (top, left, h, w) window of the padded probability map, += pixel confusion (pmf_eval_argmax)
   points  gather (or KNN vote) of the kept points' labels, += point confusion, uint32 ids     (pmf_eval_points)
 
+nuScenes (tasks/epmf_eval_nuscenes/infer.py) has six views per sweep, padded with the rows at the bottom only, and merges
+them as it goes -- SweepEvaluator:
+
+  view    per kept point (max probability, class) or the two KNN votes, merged into the sweep's running
+          (confidence, label) state where strictly more confident                              (pmf_eval_view_merge)
+  finish  after the sixth view: += point confusion over the labelled points, uint8 labels, state zeroed (pmf_eval_sweep_finish)
+
 The confusion matrices are IOUEval.conf_matrix tensors (int64, on the device) updated in place; call
 IOUEval.external_update() after a frame.  No GPU work falls back to torch: a missing kernel is an error.
 """
@@ -28,6 +35,13 @@ def pad_geometry(h, w):
     return h + h_pad, w + w_pad, h_pad // 2, w_pad // 2
 
 
+def pad_geometry_bottom(h, w):
+    """pad-to-64 of the reference's nuScenes loop: -> (H, W, 0, w_pad // 2): columns centred, rows at the bottom only
+    (ZeroPad2d((w_pad // 2, w_pad - w_pad // 2, 0, h_pad)))."""
+    H, W, _, left = pad_geometry(h, w)
+    return H, W, 0, left
+
+
 def _stream(dev):
     return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
@@ -46,14 +60,14 @@ def _check_prob(prob):
     return prob
 
 
-def eval_pre(proj, mean, stds, pcd=None, rgb=None, proj_depth=None):
+def eval_pre(proj, mean, stds, pcd=None, rgb=None, proj_depth=None, geometry=pad_geometry):
     """proj f32[10,h,w] (the V2 loader's frame); mean / stds f32[5] on the device -> (pcd [1,5,H,W], rgb [1,3,H,W],
-    proj_depth [h,w], (H, W, top, left))."""
+    proj_depth [h,w], (H, W, top, left)).  geometry: pad_geometry (centred) or pad_geometry_bottom."""
     if not (proj.is_cuda and proj.dtype == torch.float32 and proj.is_contiguous() and proj.dim() == 3
             and proj.shape[0] >= 9):
         raise ValueError("proj must be a contiguous float32 CUDA tensor [10, h, w]")
     _, h, w = proj.shape
-    H, W, top, left = pad_geometry(h, w)
+    H, W, top, left = geometry(h, w)
     dev = proj.device
     pcd = torch.empty((1, 5, H, W), dtype=torch.float32, device=dev) if pcd is None else pcd
     rgb = torch.empty((1, 3, H, W), dtype=torch.float32, device=dev) if rgb is None else rgb
@@ -189,3 +203,151 @@ class FrameEvaluator(object):
             knn_ws=self._ws("knn", (3 * K + 2,), torch.int64) if self.knn is not None else None,
             labels=self._ws("labels", (K,), torch.int32) if want_labels else None,
             labels_inv=self._ws("labels_inv", (K,), torch.int32) if lut_inv is not None else None)
+
+
+def _check_points(x_data, y_data, src):
+    K = int(x_data.shape[0])
+    for t in (x_data, y_data, src):
+        if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.dim() == 1 and t.shape[0] == K):
+            raise ValueError("x_data / y_data / src must be contiguous int32 CUDA tensors [K]")
+    return K
+
+
+def _check_state(conf_full, label_full):
+    P = int(conf_full.shape[0])
+    if not (conf_full.is_cuda and conf_full.dtype == torch.float32 and conf_full.is_contiguous() and label_full.is_cuda
+            and label_full.dtype == torch.int32 and label_full.is_contiguous() and label_full.shape[0] == P):
+        raise ValueError("conf_full must be a float32 and label_full an int32 contiguous CUDA tensor [P]")
+    return P
+
+
+def view_merge(prob, top, left, h, w, x_data, y_data, x_min, y_min, src, conf_full, label_full, argmax=None,
+               proj_range=None, unproj_range=None, knn=None, knn_ws=None, conf_ws=None):
+    """one view of a sweep into the running state conf_full f32[P] / label_full int32[P] (pmf_eval_view_merge): argmax None
+    -> (max probability, its class) at each kept point's pixel; argmax int32[h,w] -> the KNN votes over that map and over
+    the truncated confidence map (knn = (k, search, inv_gauss f32 device, cutoff), proj_range f32[h,w], unproj_range
+    f32[K]).  The state is updated in place where the view is strictly more confident."""
+    prob = _check_prob(prob)
+    Cn, H, W = prob.shape
+    dev = prob.device
+    K = _check_points(x_data, y_data, src)
+    P = _check_state(conf_full, label_full)
+    k_, search, inv_g, cutoff = (0, 0, None, 0.0) if argmax is None else knn
+    if argmax is not None:
+        if proj_range is None or unproj_range is None or unproj_range.shape[0] != K or tuple(proj_range.shape) != (h, w):
+            raise ValueError("the KNN vote needs proj_range [h, w] and unproj_range [K]")
+        if not (argmax.is_cuda and tuple(argmax.shape) == (h, w) and argmax.dtype == torch.int32):
+            raise ValueError("argmax must be an int32 CUDA tensor [h, w]")
+        if not (proj_range.is_cuda and unproj_range.is_cuda and proj_range.dtype == unproj_range.dtype == torch.float32
+                and proj_range.is_contiguous() and unproj_range.is_contiguous()):
+            raise ValueError("proj_range / unproj_range must be contiguous float32 CUDA tensors")
+        if knn_ws is None:
+            knn_ws = torch.empty(4 * K + 2, dtype=torch.int64, device=dev)
+        if conf_ws is None:
+            conf_ws = torch.empty(h * w, dtype=torch.int32, device=dev)
+    L.check(L.lib().pmf_eval_view_merge(
+        prob.data_ptr(), Cn, H, W, top, left, h, w, x_data.data_ptr(), y_data.data_ptr(), int(x_min), int(y_min), K,
+        src.data_ptr(), P, _ptr(argmax), _ptr(proj_range), _ptr(unproj_range), int(k_), int(search), _ptr(inv_g),
+        C.c_float(float(cutoff)), _ptr(knn_ws), _ptr(conf_ws), conf_full.data_ptr(), label_full.data_ptr(), _stream(dev)),
+        "pmf_eval_view_merge")
+
+
+def sweep_finish(conf_full, label_full, nclasses, sem=None, lut=None, conf=None, out_u8=None):
+    """after the last view (pmf_eval_sweep_finish): conf int64[C,C] += (label, lut[sem] where the label is non-zero, else
+    0) over the P points, out_u8 uint8[P] = label, and the state back to zero."""
+    P = _check_state(conf_full, label_full)
+    if conf is not None:
+        if not (conf.is_cuda and conf.dtype == torch.int64 and conf.is_contiguous()
+                and tuple(conf.shape) == (nclasses, nclasses)):
+            raise ValueError("conf must be a contiguous int64 CUDA tensor [%d, %d]" % (nclasses, nclasses))
+        if sem is None or lut is None or not (sem.is_cuda and lut.is_cuda and sem.dtype == lut.dtype == torch.int32
+                                              and sem.is_contiguous() and lut.is_contiguous() and sem.dim() == 1
+                                              and sem.shape[0] >= P):
+            raise ValueError("conf needs sem int32[P] and lut int32 on the device")
+    else:
+        sem = lut = None
+    if out_u8 is not None and not (out_u8.is_cuda and out_u8.dtype == torch.uint8 and out_u8.is_contiguous()
+                                   and out_u8.shape[0] >= P):
+        raise ValueError("out_u8 must be a contiguous uint8 CUDA tensor [P]")
+    L.check(L.lib().pmf_eval_sweep_finish(
+        conf_full.data_ptr(), label_full.data_ptr(), P, _ptr(sem), _ptr(lut), 0 if lut is None else int(lut.shape[0]),
+        int(nclasses), _ptr(conf), _ptr(out_u8), _stream(conf_full.device)), "pmf_eval_sweep_finish")
+    return out_u8
+
+
+class SweepEvaluator(FrameEvaluator):
+    """nuScenes: the views of one sweep at a time.  pre() / post_view() per view, finish() after the last one; the
+    running (confidence, label) state of the sweep lives on the device, sized to the largest sweep seen, zero between
+    sweeps.  Workspaces are FrameEvaluator's grow-only ones; returned tensors are views of them."""
+
+    def __init__(self, nclasses, pcd_mean, pcd_stds, knn_params=None, device="cuda"):
+        super().__init__(nclasses, pcd_mean, pcd_stds, knn_params, device)
+        self.views_in_sweep = 0
+        self.n_points = 0
+        self._conf_full = self._label_full = None
+
+    def pre(self, proj):
+        """-> (pcd [1,5,H,W], rgb [1,3,H,W]) padded at the bottom / centred columns; keeps proj_depth and the geometry."""
+        if not isinstance(proj, torch.Tensor) or proj.dim() != 3:
+            raise ValueError("proj must be a contiguous float32 CUDA tensor [10, h, w]")
+        _, h, w = proj.shape
+        H, W, _, _ = pad_geometry_bottom(h, w)
+        pcd, rgb, self.proj_depth, self.geometry = eval_pre(
+            proj, self.mean, self.stds, self._ws("pcd", (1, 5, H, W), torch.float32),
+            self._ws("rgb", (1, 3, H, W), torch.float32), self._ws("pdepth", (h, w), torch.float32),
+            geometry=pad_geometry_bottom)
+        self.proj = proj
+        return pcd, rgb
+
+    def post(self, *a, **kw):
+        raise TypeError("SweepEvaluator: use post_view() per view and finish() per sweep")
+
+    def _state(self, n_points):
+        if self._conf_full is None or self._conf_full.shape[0] < n_points:       # only between sweeps: the state is zero
+            self._conf_full = torch.zeros(n_points, dtype=torch.float32, device=self.device)
+            self._label_full = torch.zeros(n_points, dtype=torch.int32, device=self.device)
+        return self._conf_full[:n_points], self._label_full[:n_points]
+
+    def post_view(self, prob, depth, extra, pixel_conf=None):
+        """prob: the probability map [1, C, H, W] of the view pre() prepared; depth f32[K] and extra (the loader's
+        _eval_item: x_data, y_data, x_min, y_min, src, sem int32[P]); pixel_conf int64[C,C] to add the view's pixel
+        confusion to (or None).  Merges the view into the sweep's state."""
+        prob = _check_prob(prob)
+        if self.geometry is None:
+            raise RuntimeError("post_view() before pre()")
+        H, W, top, left = self.geometry
+        _, h, w = self.proj.shape
+        if tuple(prob.shape) != (self.nclasses, H, W):
+            raise ValueError("prob is %s, the view was padded to %dx%d with %d classes" % (
+                tuple(prob.shape), H, W, self.nclasses))
+        n_points = int(extra["sem"].shape[0])
+        if self.views_in_sweep and n_points != self.n_points:
+            raise RuntimeError("view of a sweep with %d points inside a sweep of %d points (finish() missing?)" % (
+                n_points, self.n_points))
+        conf_full, label_full = self._state(n_points)
+        self.n_points = n_points
+        use_knn = self.knn is not None
+        amap = None
+        if use_knn or pixel_conf is not None:
+            amap = window_argmax(prob, top, left, h, w, self.proj[9] if pixel_conf is not None else None, pixel_conf,
+                                 want_map=use_knn, out=self._ws("amap", (h, w), torch.int32) if use_knn else None)
+        K = int(extra["x_data"].shape[0])
+        view_merge(prob, top, left, h, w, extra["x_data"], extra["y_data"], extra["x_min"], extra["y_min"], extra["src"],
+                   conf_full, label_full, argmax=amap if use_knn else None, proj_range=self.proj_depth,
+                   unproj_range=depth, knn=self.knn,
+                   knn_ws=self._ws("knn", (4 * K + 2,), torch.int64) if use_knn else None,
+                   conf_ws=self._ws("cmap", (h * w,), torch.int32) if use_knn else None)
+        self.views_in_sweep += 1
+
+    def finish(self, sem, lut, n_points, point_conf=None, want_labels=True):
+        """after the last view of the sweep: point_conf int64[C,C] += the sweep's point confusion (sem int32[P] raw ids, lut
+        int32), -> uint8[P] labels (None unless want_labels); the state is zero again."""
+        if self.views_in_sweep == 0:
+            raise RuntimeError("finish() without a view")
+        if int(n_points) != self.n_points:
+            raise RuntimeError("finish() for %d points, the sweep's views carried %d" % (int(n_points), self.n_points))
+        conf_full, label_full = self._state(self.n_points)
+        out = sweep_finish(conf_full, label_full, self.nclasses, sem, lut, point_conf,
+                           self._ws("labels_u8", (self.n_points,), torch.uint8) if want_labels else None)
+        self.views_in_sweep = 0
+        return out
