@@ -645,6 +645,21 @@ int pmf_eval_view_merge(const float* prob, int32_t C, int32_t H, int32_t W, int3
  * label_full[p] = 0 for the next sweep.  P == 0 is a no-op. */
 int pmf_eval_sweep_finish(float* conf_full, int32_t* label_full, int64_t P, const int32_t* sem, const int32_t* lut,
                           int32_t nlut, int32_t C, int64_t* conf, uint8_t* out_u8, pmf_stream_t s);
+/* ---- SalsaNext evaluation on range images, B sweeps per call (tasks/salsanext_eval_nuscenes/infer.py:90-119) -----------
+ * Every sweep has the same H x W (sensor.proj_h x proj_w), so the maps of a forward are one batch; the points of the B sweeps
+ * are concatenated, sweep b owning [offsets[b], offsets[b + 1]) (offsets int64[B + 1] on the device, offsets[B] == P_total).
+ * pmf_eval_range_batch, at most two launches.  Map stage: argmax_ws int32[B*H*W] = class argmax of prob f32[B][C][H][W]
+ * (ties -> lowest class, NaN wins: torch.argmax); pixel_conf (optional, needs label f32[B][H][W]) int64[C][C] +=
+ * (argmax, label) over all pixels, labels outside [0, C) not counted.  Point stage, per point p of sweep b at column px[p],
+ * row py[p]: knn == 0: labels[p] = argmax_ws[b][py][px] (a pixel outside the map gives 0); knn > 0: the vote of pmf_knn_vote
+ * on (proj_range[b], unproj_range[p], argmax_ws[b], px, py) with the same device code, bit-identical labels.  point_conf
+ * (optional) int64[C][C] += (labels[p], lut[sem[p]]), sem int32[P_total] raw ids, ids outside the lut -> class 0.
+ * C <= 64, B <= 1024.  B == 0 is a no-op; P_total == 0 skips the point stage.  search must be odd (-1 otherwise). */
+int pmf_eval_range_batch(const float* prob, int32_t B, int32_t C, int32_t H, int32_t W, const float* label,
+                         const float* proj_range, const int64_t* offsets, int64_t P_total, const int32_t* px,
+                         const int32_t* py, const float* unproj_range, const int32_t* sem, const int32_t* lut, int32_t nlut,
+                         int32_t knn, int32_t search, const float* inv_gauss, float cutoff, int32_t* argmax_ws,
+                         int32_t* labels, int64_t* pixel_conf, int64_t* point_conf, pmf_stream_t s);
 /* pixel splits pmf_conv_wgrad will use for this descriptor (sizes `partial`) */
 int pmf_conv_wgrad_nsplit(const pmf_wgrad_desc_t* d);
 /* the kernel family pmf_conv_wgrad runs for this descriptor under the current PMF_WG_* switches (the same selection that

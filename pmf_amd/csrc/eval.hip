@@ -6,10 +6,12 @@
 //                    contiguous copy) -> optional int32[h,w] map, optional += [C][C] pixel confusion (pred, label)
 //   pmf_eval_points  labels of the K kept points: a gather of the argmax straight from the probability window, or the
 //                    KNN vote of knn.hip on the int32 map; += [C][C] point confusion, optional uint32 inverse-mapped ids
+//   pmf_eval_range_batch  SalsaNext range images (every sweep 32x2048 on nuScenes), B sweeps per call: section (e)
 // Ties of the argmax go to the lowest class and a NaN wins (torch.argmax).  Confusion counts are per-workgroup LDS
 // histograms flushed with 64-bit global atomics (as loss.hip's fused loss does); all stores are vector stores.
 #include "common.h"
 #pragma clang fp contract(off)
+#include "knn_vote.h"
 
 #define EV_MAXC 64          // classes of an LDS confusion histogram (16 KB)
 #define EV_GRID 1024        // workgroup cap of the grid-stride kernels (bounds the histogram flushes)
@@ -343,6 +345,120 @@ extern "C" int pmf_eval_sweep_finish(float* conf_full, int32_t* label_full, int6
   const int64_t g = cdiv64(P, 256);
   hipLaunchKernelGGL(eval_sweep_finish_k, dim3((unsigned)(g < EV_GRID ? g : EV_GRID)), dim3(256), 0, (hipStream_t)s,
                      conf_full, label_full, P, sem, lut, nlut, C, (unsigned long long*)conf, out_u8);
+  PMF_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- (e) SalsaNext range images: B sweeps per call ---------------------------------------------------------------------
+// (tasks/salsanext_eval_nuscenes/infer.py:90-119 of the reference, per sweep: argmax, IOUEval.addBatch on the pixels, KNN or
+// pred_argmax[uproj_y_idx, uproj_x_idx], .cpu(), IOUEval.addBatch on the points.)  Every sweep has the same H x W, so the B
+// maps of a forward are one [B, C, H, W] tensor and everything behind the network is two launches: the vote reads the
+// FINISHED argmax of its neighbours, so the map stage and the point stage cannot share one.
+// Map stage: one lane per pixel of the B maps (C coalesced plane reads), int32 argmax + pixel confusion.
+__global__ __launch_bounds__(256) void eval_range_map_k(const float* __restrict__ prob, int C, int64_t HW, int64_t total,
+                                                        const float* __restrict__ label, int32_t* __restrict__ amap,
+                                                        unsigned long long* __restrict__ conf) {
+  __shared__ unsigned hist[EV_MAXC * EV_MAXC];
+  if (conf) ev_hist_zero(hist, C);
+  for (int64_t q = blockIdx.x * (int64_t)256 + threadIdx.x; q < total; q += (int64_t)gridDim.x * 256) {
+    const int64_t b = q / HW;
+    const float* p = prob + b * C * HW + (q - b * HW);
+    float best = 0.f;
+    int bi = 0;
+    for (int c = 0; c < C; ++c) ev_take(p[(int64_t)c * HW], c, best, bi);
+    amap[q] = bi;
+    if (conf) {
+      const int t = (int)label[q];
+      if (t >= 0 && t < C) atomicAdd(&hist[bi * C + t], 1u);
+    }
+  }
+  if (conf) ev_hist_flush(hist, C, conf);
+}
+
+// Point stage: one lane per point, a workgroup is 256 consecutive points of ONE sweep (knn_wg_frame: the offsets table is
+// walked once per workgroup with scalar loads, not per lane).  S = 0: the label at the point's pixel; 3 / 5: the vote of
+// knn_vote.h with the window staged through LDS; 7: gathered window; -1: any other odd window.  The same device
+// functions as pmf_knn_vote: bit-identical labels.  The label goes out as int32 and into the workgroup's histogram.
+template <int S>
+__global__ __launch_bounds__(256) void eval_range_points_k(const int32_t* __restrict__ amap, const float* __restrict__ pr,
+                                                           int B, int H, int W, const int64_t* __restrict__ offsets,
+                                                           int64_t P_total, const int32_t* __restrict__ px,
+                                                           const int32_t* __restrict__ py, const float* __restrict__ ur,
+                                                           int knn, int search, const float* __restrict__ invg, float cutoff,
+                                                           int C, const int32_t* __restrict__ sem,
+                                                           const int32_t* __restrict__ lut, int nlut,
+                                                           int32_t* __restrict__ labels,
+                                                           unsigned long long* __restrict__ conf) {
+  __shared__ unsigned hist[EV_MAXC * EV_MAXC];
+  int b, wg;
+  int64_t lo, hi;
+  knn_wg_frame(offsets, B, 0, b, wg, lo, hi);
+  if (b < 0) return;                                    // (the grid is an upper bound; uniform over the workgroup)
+  if (conf) ev_hist_zero(hist, C);
+  const int64_t i = lo + (int64_t)wg * 256 + threadIdx.x;
+  const bool valid = i < hi && i >= 0 && i < P_total;
+  const int32_t* __restrict__ amb = amap + (size_t)b * H * W;
+  int cx = 0, cy = 0;
+  if (valid) { cx = px[i]; cy = py[i]; }
+  int pred = 0;
+  if constexpr (S == 0) {
+    if (valid && cx >= 0 && cx < W && cy >= 0 && cy < H) pred = amb[(size_t)cy * W + cx];
+  } else {
+    const float* __restrict__ prb = pr + (size_t)b * H * W;
+    const float r = valid ? ur[i] : 0.f;
+    if constexpr (S == 3 || S == 5) {
+      pred = knn_vote_lds<S>(prb, nullptr, amb, valid, cx, cy, r, H, W, knn, invg, cutoff, C);
+    } else if constexpr (S == 7) {
+      if (valid) pred = knn_vote_gather<7>(prb, nullptr, amb, cx, cy, r, H, W, knn, invg, cutoff, C);
+    } else {
+      if (valid) pred = knn_vote_any(prb, nullptr, amb, cx, cy, r, H, W, knn, search, invg, cutoff, C);
+    }
+  }
+  if (valid) {
+    labels[i] = pred;
+    if (conf) {
+      const int sl = sem[i];
+      const int t = (sl >= 0 && sl < nlut) ? lut[sl] : 0;
+      if (t >= 0 && t < C && pred >= 0 && pred < C) atomicAdd(&hist[pred * C + t], 1u);
+    }
+  }
+  if (conf) ev_hist_flush(hist, C, conf);
+}
+
+extern "C" int pmf_eval_range_batch(const float* prob, int32_t B, int32_t C, int32_t H, int32_t W, const float* label,
+                                    const float* proj_range, const int64_t* offsets, int64_t P_total, const int32_t* px,
+                                    const int32_t* py, const float* unproj_range, const int32_t* sem, const int32_t* lut,
+                                    int32_t nlut, int32_t knn, int32_t search, const float* inv_gauss, float cutoff,
+                                    int32_t* argmax_ws, int32_t* labels, int64_t* pixel_conf, int64_t* point_conf,
+                                    pmf_stream_t s) {
+  if (B < 0 || B > 1024 || C < 1 || C > EV_MAXC || H < 1 || W < 1 || P_total < 0 || knn < 0) return PMF_E_ARG;
+  if (knn > 0) {
+    if (search % 2 == 0 || search < 1 || search > 255) return PMF_E_ARG;      // knn.py:73-74 raises ValueError
+    if (knn > 8 || knn > search * search) return PMF_E_UNSUPPORTED;
+  }
+  if (B == 0) return 0;
+  if (!prob || !argmax_ws || (pixel_conf && !label)) return PMF_E_ARG;
+  hipStream_t st = (hipStream_t)s;
+  const int64_t total = (int64_t)B * H * W;
+  const int64_t g = cdiv64(total, 256);
+  hipLaunchKernelGGL(eval_range_map_k, dim3((unsigned)(g < EV_GRID ? g : EV_GRID)), dim3(256), 0, st, prob, C,
+                     (int64_t)H * W, total, label, argmax_ws, (unsigned long long*)pixel_conf);
+  PMF_LAUNCH_CHECK();
+  if (P_total == 0) return 0;
+  if (!offsets || !px || !py || !labels) return PMF_E_ARG;
+  if (point_conf && (!sem || !lut || nlut < 1)) return PMF_E_ARG;
+  if (knn > 0 && (!proj_range || !unproj_range || !inv_gauss)) return PMF_E_ARG;
+  const dim3 grid((unsigned)(cdiv64(P_total, 256) + B)), block(256);        // sum_b ceil(n_b / 256) <= ceil(P / 256) + B
+#define EV_RANGE_POINTS(S)                                                                                                 \
+  hipLaunchKernelGGL(eval_range_points_k<S>, grid, block, 0, st, argmax_ws, proj_range, B, H, W, offsets, P_total, px, py, \
+                     unproj_range, knn, search, inv_gauss, cutoff, C, sem, lut, nlut, labels,                              \
+                     (unsigned long long*)point_conf)
+  if (knn == 0) EV_RANGE_POINTS(0);
+  else if (search == 3) EV_RANGE_POINTS(3);
+  else if (search == 5) EV_RANGE_POINTS(5);
+  else if (search == 7) EV_RANGE_POINTS(7);
+  else EV_RANGE_POINTS(-1);
+#undef EV_RANGE_POINTS
   PMF_LAUNCH_CHECK();
   return 0;
 }

@@ -3,8 +3,11 @@
 // S*S window (weighted |range difference| and neighbour labels) in registers, selects the k smallest by
 // repeated first-minimum (ties -> smaller window index, the rule the CPU oracle pins) and votes.
 // HBM-bound: algorithmic bytes 12*H*W + 28*P per call.
+// The vote itself (window, selection, majority) is the set of device functions of knn_vote.h; the kernels here resolve the
+// frame and the point and store int64 labels.
 #include "common.h"
 #pragma clang fp contract(off)
+#include "knn_vote.h"
 
 template <int S>
 __global__ __launch_bounds__(256) void knn_k(const float* __restrict__ pr, const float* __restrict__ ur,
@@ -12,66 +15,19 @@ __global__ __launch_bounds__(256) void knn_k(const float* __restrict__ pr, const
                                              const int64_t* __restrict__ py, int H, int W, int64_t P, int knn,
                                              const float* __restrict__ invg, float cutoff, int nclasses,
                                              int64_t* __restrict__ labels, const int32_t* __restrict__ am32 = nullptr) {
-  constexpr int S2 = S * S, PAD = (S - 1) / 2, CENTER = (S2 - 1) / 2;
+  constexpr int S2 = S * S;
   __shared__ float wsh[S2];
   if (threadIdx.x < S2) wsh[threadIdx.x] = invg[threadIdx.x];
   __syncthreads();
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= P) return;
-  const int cx = (int)px[i], cy = (int)py[i];
-  const float r = ur[i];
-  float dist[S2];
-  int lab[S2];
-#pragma unroll
-  for (int t = 0; t < S2; ++t) {
-    const int y = cy + t / S - PAD, x = cx + t % S - PAD;
-    float v = 0.f;   // F.unfold zero padding: range 0, label 0
-    int l = 0;
-    if (y >= 0 && y < H && x >= 0 && x < W) {
-      v = pr[(size_t)y * W + x];
-      l = am32 ? am32[(size_t)y * W + x] : (int)am[(size_t)y * W + x];
-      if (v < 0.f) v = INFINITY;
-    }
-    if (t == CENTER) v = r;
-    dist[t] = fabsf(v - r) * wsh[t];   // |neigh - range| * (1 - gauss), float32, knn.py:97-108
-    lab[t] = l;
-  }
-  // k x first-minimum selection
-  unsigned long long used = 0ull;
-  int sel[S2 < 8 ? 8 : 8];
-  int nsel = knn < 8 ? knn : 8;
-  for (int k = 0; k < nsel; ++k) {
-    float best = 0.f;
-    int bi = -1;
-#pragma unroll
-    for (int t = 0; t < S2; ++t) {
-      const bool free_ = !((used >> t) & 1ull);
-      if (free_ && (bi < 0 || dist[t] < best)) { best = dist[t]; bi = t; }
-    }
-    used |= 1ull << bi;
-    int l = 0;
-#pragma unroll
-    for (int t = 0; t < S2; ++t) if (t == bi) l = lab[t];
-    if (cutoff > 0.f && best > cutoff) l = nclasses;
-    sel[k] = l;
-  }
-  int best_cnt = 0, best_cls = 1;
-  for (int a = 0; a < nsel; ++a) {
-    const int cls = sel[a];
-    if (cls < 1 || cls >= nclasses) continue;
-    int cnt = 0;
-    for (int b = 0; b < nsel; ++b) cnt += sel[b] == cls;
-    if (cnt > best_cnt || (cnt == best_cnt && cls < best_cls)) { best_cnt = cnt; best_cls = cls; }
-  }
-  labels[i] = best_cls;
+  labels[i] = knn_vote_gather<S>(pr, am, am32, (int)px[i], (int)py[i], ur[i], H, W, knn, wsh, cutoff, nclasses);
 }
 
 // ---- any odd window (search = 1, 9, 11, ...; the reference accepts every odd size, knn.py:73-74; the nuScenes config ships
 // search 11, tasks/pmf_eval_nuscenes/config_server_nus.yaml) -------------------------------------------------------------
-// One lane per point, window size at run time.  k x first-minimum with ties -> smaller window index is what a STABLE
-// insertion into an ascending list of length k produces (an equal distance seen later never moves in front of an earlier
-// one); the vote only counts labels, so the order inside the list does not matter.  Same float32 arithmetic as knn_k:
-// bit-identical labels where both apply (tests).  Frames of a batch through the offsets table (nullptr: one frame).
+// One lane per point, window size at run time (knn_vote_any): bit-identical labels to knn_k where both apply (tests).
+// Frames of a batch through the offsets table (nullptr: one frame).
 __global__ __launch_bounds__(64) void knn_any_k(const float* __restrict__ pr, const float* __restrict__ ur,
                                                 const int64_t* __restrict__ am, const int64_t* __restrict__ px,
                                                 const int64_t* __restrict__ py, const int64_t* __restrict__ offsets, int B,
@@ -85,54 +41,7 @@ __global__ __launch_bounds__(64) void knn_any_k(const float* __restrict__ pr, co
   const float* __restrict__ prb = pr + (size_t)b * H * W;
   const int64_t* __restrict__ amb = am + (size_t)b * H * W;
   const int32_t* __restrict__ amb32 = am32 ? am32 + (size_t)b * H * W : nullptr;
-  const int cx = (int)px[i], cy = (int)py[i], PAD = (S - 1) / 2, CENTER = (S * S - 1) / 2;
-  const float r = ur[i];
-  float bd[8];
-  int bl[8];
-  const int nsel = knn < 8 ? knn : 8;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) { bd[k] = INFINITY; bl[k] = 0; }
-  int filled = 0;
-  for (int ty = 0, t = 0; ty < S; ++ty)
-    for (int tx = 0; tx < S; ++tx, ++t) {
-      const int y = cy + ty - PAD, x = cx + tx - PAD;
-      float v = 0.f;
-      int l = 0;
-      if (y >= 0 && y < H && x >= 0 && x < W) {
-        v = prb[(size_t)y * W + x];
-        l = amb32 ? amb32[(size_t)y * W + x] : (int)amb[(size_t)y * W + x];
-        if (v < 0.f) v = INFINITY;
-      }
-      if (t == CENTER) v = r;
-      float d = fabsf(v - r) * invg[t];
-      // position = number of kept entries with distance <= d (stable); NaN-free: distances are >= 0 or +inf
-      int pos = 0;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) pos += (k < filled && bd[k] <= d) ? 1 : 0;
-      if (pos < nsel) {
-#pragma unroll
-        for (int k = 7; k > 0; --k)
-          if (k > pos && k < nsel) { bd[k] = bd[k - 1]; bl[k] = bl[k - 1]; }
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-          if (k == pos) { bd[k] = d; bl[k] = l; }
-        filled = filled < nsel ? filled + 1 : filled;
-      }
-    }
-  int best_cnt = 0, best_cls = 1;
-  for (int a = 0; a < nsel; ++a) {
-    int cls = bl[a];
-    if (cutoff > 0.f && bd[a] > cutoff) cls = nclasses;
-    if (cls < 1 || cls >= nclasses) continue;
-    int cnt = 0;
-    for (int c = 0; c < nsel; ++c) {
-      int cc = bl[c];
-      if (cutoff > 0.f && bd[c] > cutoff) cc = nclasses;
-      cnt += cc == cls;
-    }
-    if (cnt > best_cnt || (cnt == best_cnt && cls < best_cls)) { best_cnt = cnt; best_cls = cls; }
-  }
-  labels[i] = best_cls;
+  labels[i] = knn_vote_any(prb, amb, amb32, (int)px[i], (int)py[i], ur[i], H, W, knn, S, invg, cutoff, nclasses);
 }
 
 template <int S>
@@ -182,7 +91,7 @@ __global__ __launch_bounds__(64) void knn_batch_k(const float* __restrict__ pr, 
                                                   int B, int H, int W, int64_t P, int knn, const float* __restrict__ invg,
                                                   float cutoff, int nclasses, int64_t* __restrict__ labels,
                                                   const int32_t* __restrict__ am32 = nullptr) {
-  constexpr int S2 = S * S, PAD = (S - 1) / 2, CENTER = (S2 - 1) / 2;
+  constexpr int S2 = S * S;
   __shared__ float wsh[S2];
   if (threadIdx.x < S2) wsh[threadIdx.x] = invg[threadIdx.x];
   __syncthreads();
@@ -193,63 +102,13 @@ __global__ __launch_bounds__(64) void knn_batch_k(const float* __restrict__ pr, 
   const float* __restrict__ prb = pr + (size_t)b * H * W;
   const int64_t* __restrict__ amb = am + (size_t)b * H * W;
   const int32_t* __restrict__ amb32 = am32 ? am32 + (size_t)b * H * W : nullptr;
-  const int cx = (int)px[i], cy = (int)py[i];
-  const float r = ur[i];
-  float dist[S2];
-  int lab[S2];
-#pragma unroll
-  for (int t = 0; t < S2; ++t) {
-    const int y = cy + t / S - PAD, x = cx + t % S - PAD;
-    float v = 0.f;
-    int l = 0;
-    if (y >= 0 && y < H && x >= 0 && x < W) {
-      v = prb[(size_t)y * W + x];
-      l = amb32 ? amb32[(size_t)y * W + x] : (int)amb[(size_t)y * W + x];
-      if (v < 0.f) v = INFINITY;
-    }
-    if (t == CENTER) v = r;
-    dist[t] = fabsf(v - r) * wsh[t];
-    lab[t] = l;
-  }
-  unsigned long long used = 0ull;
-  int sel[8];
-  int nsel = knn < 8 ? knn : 8;
-  for (int k = 0; k < nsel; ++k) {
-    float best = 0.f;
-    int bi = -1;
-#pragma unroll
-    for (int t = 0; t < S2; ++t) {
-      const bool free_ = !((used >> t) & 1ull);
-      if (free_ && (bi < 0 || dist[t] < best)) { best = dist[t]; bi = t; }
-    }
-    used |= 1ull << bi;
-    int l = 0;
-#pragma unroll
-    for (int t = 0; t < S2; ++t) if (t == bi) l = lab[t];
-    if (cutoff > 0.f && best > cutoff) l = nclasses;
-    sel[k] = l;
-  }
-  int best_cnt = 0, best_cls = 1;
-  for (int a = 0; a < nsel; ++a) {
-    const int cls = sel[a];
-    if (cls < 1 || cls >= nclasses) continue;
-    int cnt = 0;
-    for (int c = 0; c < nsel; ++c) cnt += sel[c] == cls;
-    if (cnt > best_cnt || (cnt == best_cnt && cls < best_cls)) { best_cnt = cnt; best_cls = cls; }
-  }
-  labels[i] = best_cls;
+  labels[i] = knn_vote_gather<S>(prb, amb, amb32, (int)px[i], (int)py[i], ur[i], H, W, knn, wsh, cutoff, nclasses);
 }
 
-// ---- the same vote with the window staged through LDS ------------------------------------------------------------------
-// A gather of one window tap touches one cache line PER LANE when the lanes of a wave sit on different image rows -- and in
-// sweep-file order (azimuth by azimuth) consecutive points are the lasers of one column: 50 fully divergent gathers per
-// point, the texture-address unit processes them line by line (21 us for 102 k points; random order 33 us).  Here a workgroup
-// of 256 consecutive points of ONE frame takes the bounding box of its points (+ the window margin): in sweep order that is
-// ~5 columns x all rows, a few hundred pixels; (range, label) of the box are staged into LDS once (rows of the box are
-// contiguous: ~10 wave loads per map) and all window taps are read from there.  Zero padding / negative-range handling
-// happen at staging time with the same rules, the selection and the vote are the code above: bit-identical labels.  A box
-// above KNN_LDS_PIX pixels (points in random order) uses the global gathers as before, decided per workgroup.
-#define KNN_LDS_PIX 4096
+// ---- the same vote with the window staged through LDS (knn_vote_lds) ---------------------------------------------------
+// A workgroup is 256 consecutive points of ONE frame: frame b owns ceil(n_b / 256) consecutive workgroups (knn_wg_frame).
+// (Measured: indexing the concatenated list directly, so that the point loads do not wait for the frame walk, is SLOWER
+// -- 13.2 vs 11.7 us -- the per-thread frame search and the mixed-frame handling cost more than the overlap gives.)
 template <int S>
 __global__ __launch_bounds__(256) void knn_batch_lds_k(const float* __restrict__ pr, const float* __restrict__ ur,
                                                        const int64_t* __restrict__ am, const int64_t* __restrict__ px,
@@ -257,28 +116,9 @@ __global__ __launch_bounds__(256) void knn_batch_lds_k(const float* __restrict__
                                                        int B, int H, int W, int64_t P1, int knn, const float* __restrict__ invg,
                                                        float cutoff, int nclasses, int64_t* __restrict__ labels,
                                                        const int32_t* __restrict__ am32) {
-  constexpr int S2 = S * S, PAD = (S - 1) / 2, CENTER = (S2 - 1) / 2;
-  __shared__ float s_v[KNN_LDS_PIX];
-  __shared__ int s_l[KNN_LDS_PIX];
-  __shared__ int s_wbox[4][4];          // per wave: min x, max x, min y, max y (no initialisation, no atomics: one barrier less)
-  // frame of this workgroup: frame b owns ceil(n_b / 256) consecutive workgroups.  B is small; the walk has no early exit so
-  // that its scalar loads are independent of each other (one memory latency, not one per frame).  (Measured: indexing the
-  // concatenated list directly, so that the point loads do not wait for this walk, is SLOWER -- 13.2 vs 11.7 us -- the
-  // per-thread frame search and the mixed-frame handling cost more than the overlap gives.)
-  int b = -1, wg = 0;
-  int64_t lo = 0, hi = 0;
-  if (!offsets) { b = 0; wg = (int)blockIdx.x; hi = P1; }        // one frame of P1 points (pmf_knn_vote): no table
-  else {
-    int first = 0;
-    int64_t o0 = offsets[0];
-    for (int k = 0; k < B; ++k) {
-      const int64_t o1 = offsets[k + 1];
-      const int nb = (int)((o1 - o0 + 255) >> 8);
-      if (b < 0 && (int)blockIdx.x < first + nb) { b = k; wg = (int)blockIdx.x - first; lo = o0; hi = o1; }
-      first += nb;
-      o0 = o1;
-    }
-  }
+  int b, wg;
+  int64_t lo, hi;
+  knn_wg_frame(offsets, B, P1, b, wg, lo, hi);
   if (b < 0) return;                                    // (the grid is an upper bound)
   const int64_t i = lo + (int64_t)wg * 256 + threadIdx.x;
   const bool valid = i < hi;
@@ -288,113 +128,8 @@ __global__ __launch_bounds__(256) void knn_batch_lds_k(const float* __restrict__
   int cx = 0, cy = 0;
   float r = 0.f;
   if (valid) { cx = (int)px[i]; cy = (int)py[i]; r = ur[i]; }
-  {
-    // bounding box: butterfly over the wave, one LDS atomic per wave and bound.  (Points far outside the image only enlarge
-    // the box: it then exceeds the LDS budget and the global path, which clips tap by tap, takes over.)
-    int mnx = valid ? cx : 0x7fffffff, mxx = valid ? cx : -0x7fffffff, mny = valid ? cy : 0x7fffffff, mxy = valid ? cy : -0x7fffffff;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      mnx = min(mnx, __shfl_xor(mnx, o)); mxx = max(mxx, __shfl_xor(mxx, o));
-      mny = min(mny, __shfl_xor(mny, o)); mxy = max(mxy, __shfl_xor(mxy, o));
-    }
-    if ((threadIdx.x & 63) == 0) {
-      int* wb = s_wbox[threadIdx.x >> 6];
-      wb[0] = mnx; wb[1] = mxx; wb[2] = mny; wb[3] = mxy;
-    }
-  }
-  __syncthreads();
-  const int bx0 = min(min(s_wbox[0][0], s_wbox[1][0]), min(s_wbox[2][0], s_wbox[3][0]));
-  const int bx1 = max(max(s_wbox[0][1], s_wbox[1][1]), max(s_wbox[2][1], s_wbox[3][1]));
-  const int by0 = min(min(s_wbox[0][2], s_wbox[1][2]), min(s_wbox[2][2], s_wbox[3][2]));
-  const int by1 = max(max(s_wbox[0][3], s_wbox[1][3]), max(s_wbox[2][3], s_wbox[3][3]));
-  const int x0 = bx0 - PAD, y0 = by0 - PAD;
-  const long bw = (long)bx1 - bx0 + 1 + 2 * PAD, bh = (long)by1 - by0 + 1 + 2 * PAD;
-  const bool staged = bw > 0 && bh > 0 && bw * bh <= KNN_LDS_PIX;
-  if (staged) {
-    // all loads of the box first (up to 16 pixels per thread, independent), then the LDS stores: one memory latency
-    constexpr int PER = KNN_LDS_PIX / 256;
-    const int n = (int)(bw * bh), w_ = (int)bw;
-    const float inv_w = 1.f / (float)w_;
-    float vv[PER];
-    int ll[PER];
-#pragma unroll
-    for (int u = 0; u < PER; ++u) {
-      const int j = threadIdx.x + u * 256;
-      vv[u] = 0.f; ll[u] = 0;   // F.unfold zero padding: range 0, label 0
-      if (j < n) {
-        int yy = (int)(((float)j + 0.5f) * inv_w);       // j < 4096, w_ >= S: exact up to one step, corrected below
-        int xx = j - yy * w_;
-        if (xx < 0) { --yy; xx += w_; } else if (xx >= w_) { ++yy; xx -= w_; }
-        const int y = y0 + yy, x = x0 + xx;
-        if (y >= 0 && y < H && x >= 0 && x < W) {
-          vv[u] = prb[(size_t)y * W + x];
-          ll[u] = amb32 ? amb32[(size_t)y * W + x] : (int)amb[(size_t)y * W + x];
-        }
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < PER; ++u) {
-      const int j = threadIdx.x + u * 256;
-      if (j < n) { s_v[j] = vv[u] < 0.f ? INFINITY : vv[u]; s_l[j] = ll[u]; }
-    }
-  }
-  __syncthreads();
-  if (!valid) return;
-  float dist[S2];
-  int lab[S2];
-  if (staged) {
-    const int w_ = (int)bw, base = (cy - PAD - y0) * w_ + (cx - PAD - x0);
-#pragma unroll
-    for (int t = 0; t < S2; ++t) {
-      const int j = base + (t / S) * w_ + (t % S);
-      float v = s_v[j];
-      if (t == CENTER) v = r;
-      dist[t] = fabsf(v - r) * invg[t];
-      lab[t] = s_l[j];
-    }
-  } else {
-#pragma unroll
-    for (int t = 0; t < S2; ++t) {
-      const int y = cy + t / S - PAD, x = cx + t % S - PAD;
-      float v = 0.f;
-      int l = 0;
-      if (y >= 0 && y < H && x >= 0 && x < W) {
-        v = prb[(size_t)y * W + x];
-        l = amb32 ? amb32[(size_t)y * W + x] : (int)amb[(size_t)y * W + x];
-        if (v < 0.f) v = INFINITY;
-      }
-      if (t == CENTER) v = r;
-      dist[t] = fabsf(v - r) * invg[t];
-      lab[t] = l;
-    }
-  }
-  // k x first-minimum selection (ties -> smaller window index), the same rule as knn_k with a 32-bit taken mask (S2 <= 25 on
-  // this path) and the label carried along the scan
-  static_assert(S2 <= 32, "taken mask");
-  unsigned used = 0u;
-  int sel[8];
-  int nsel = knn < 8 ? knn : 8;
-  for (int k = 0; k < nsel; ++k) {
-    float best = 0.f;
-    int bi = -1, l = 0;
-#pragma unroll
-    for (int t = 0; t < S2; ++t) {
-      const bool take = !(used & (1u << t)) && (bi < 0 || dist[t] < best);
-      best = take ? dist[t] : best; l = take ? lab[t] : l; bi = take ? t : bi;
-    }
-    used |= 1u << bi;
-    if (cutoff > 0.f && best > cutoff) l = nclasses;
-    sel[k] = l;
-  }
-  int best_cnt = 0, best_cls = 1;
-  for (int a = 0; a < nsel; ++a) {
-    const int cls = sel[a];
-    if (cls < 1 || cls >= nclasses) continue;
-    int cnt = 0;
-    for (int c = 0; c < nsel; ++c) cnt += sel[c] == cls;
-    if (cnt > best_cnt || (cnt == best_cnt && cls < best_cls)) { best_cnt = cnt; best_cls = cls; }
-  }
-  labels[i] = best_cls;
+  const int lab = knn_vote_lds<S>(prb, amb, amb32, valid, cx, cy, r, H, W, knn, invg, cutoff, nclasses);
+  if (valid) labels[i] = lab;
 }
 
 int knn_vote_batch_impl(const float* proj_range, const float* unproj_range, const int64_t* proj_argmax,

@@ -4,7 +4,9 @@ Same constructor / item contract as the reference: (proj_feature [5,H,W], proj_s
 with return_uproj, (+ proj_range, uproj_x, uproj_y, uproj_depth).  The sweep goes to the GPU once; augmentation
 (pmf_points_transform), projection (pmf_range_project_index) and the tensor assembly incl. normalisation and label
 lookup (pmf_range_project_gather) are HIP kernels, and the item stays on the device -- feed it to SalsaNext directly.
-``dataset`` duck type: loadDataByIndex(i) -> (pointcloud [P,4], sem_label [P], inst_label), labelMapping(labels)."""
+``dataset`` duck type: loadDataByIndex(i) -> (pointcloud [P,4], sem_label [P], inst_label), labelMapping(labels).
+Evaluation (tasks/salsanext_eval_nuscenes) uses _eval_item: the same item plus the raw per-point ids and the label table on
+the device, from ONE loadDataByIndex call."""
 import numpy as np
 import torch
 from torch.utils.data import Dataset
@@ -33,6 +35,48 @@ class SalsaNextLoader(Dataset):
         self.proj_img_mean = torch.tensor(s["img_mean"], dtype=torch.float)
         self.proj_img_stds = torch.tensor(s["img_stds"], dtype=torch.float)
         self._mean_dev = self._stds_dev = None
+        self._lut = None
+
+    def _label_lut(self):
+        """int32[256] on the device: raw id -> class.  The dataset's map_name_from_general_index_to_segmentation_index (nuScenes)
+        or class_map_lut table when it has one, else labelMapping evaluated once on all 256 ids."""
+        if self._lut is None:
+            ds = self.dataset
+            lut = np.zeros(256, np.int32)
+            table = getattr(ds, "map_name_from_general_index_to_segmentation_index", None)
+            if table is not None:
+                keys = sorted(k for k in table if 0 <= int(k) < 256)
+                lut[keys] = [int(table[k]) for k in keys]
+            elif getattr(ds, "class_map_lut", None) is not None:
+                t = np.asarray(ds.class_map_lut).astype(np.int32).reshape(-1)[:256]
+                lut[:t.shape[0]] = t
+            else:
+                lut[:] = np.asarray(ds.labelMapping(np.arange(256, dtype=np.uint8)[:, None])).reshape(-1)
+            self._lut = torch.from_numpy(lut).to(self.device)
+        return self._lut
+
+    def _eval_item(self, index):
+        """evaluation item (is_train=False): dict(feature f32[5,H,W], label f32[H,W], mask i32[H,W], proj_range f32[H,W],
+        px / py int32[P] (column / row), depth f32[P], sem int32[P] raw ids, lut int32[256]), all on the device.  One
+        loadDataByIndex call and no host label pass: the raw ids go to the device once and the pixel labels are
+        lut[sem] there (the reference's loop loads every sweep a second time for its point labels)."""
+        pointcloud, sem_label, _ = self.dataset.loadDataByIndex(index)
+        pts = self.projection.to_device(pointcloud)
+        raw = sem_label if isinstance(sem_label, torch.Tensor) else torch.from_numpy(
+            np.ascontiguousarray(np.asarray(sem_label).reshape(-1)).astype(np.int32))
+        sem = raw.reshape(-1).to(self.device, torch.int32)
+        lut = self._label_lut()
+        idx = sem.long()
+        inside = (idx >= 0) & (idx < lut.shape[0])
+        mapped = torch.where(inside, lut[idx.clamp(0, lut.shape[0] - 1)], torch.zeros_like(sem))   # outside the table: class 0,
+        #                                                                                    the rule of the point stage
+        if self._mean_dev is None:
+            self._mean_dev = self.proj_img_mean.to(self.device)
+            self._stds_dev = self.proj_img_stds.to(self.device)
+        feat, label, mask, rng = self.projection.loader_item(pts, mapped, self._mean_dev, self._stds_dev)
+        c = self.projection.cached_data
+        return dict(feature=feat, label=label, mask=mask, proj_range=rng, px=c["uproj_x_idx"], py=c["uproj_y_idx"],
+                    depth=c["uproj_depth"], sem=sem, lut=lut)
 
     def __getitem__(self, index):
         pointcloud, sem_label, inst_label = self.dataset.loadDataByIndex(index)

@@ -15,6 +15,12 @@ them as it goes -- SweepEvaluator:
           (confidence, label) state where strictly more confident                              (pmf_eval_view_merge)
   finish  after the sixth view: += point confusion over the labelled points, uint8 labels, state zeroed (pmf_eval_sweep_finish)
 
+SalsaNext range images (tasks/salsanext_eval_nuscenes/infer.py) all have the sensor's proj_h x proj_w, so B sweeps go
+through the network per forward and everything behind it is one batched pass -- RangeSweepEvaluator:
+
+  range   argmax of the B maps, += pixel confusion; per point the label at its pixel or the KNN vote, int32 labels,
+          += point confusion: two launches per batch                                          (pmf_eval_range_batch)
+
 The confusion matrices are IOUEval.conf_matrix tensors (int64, on the device) updated in place; call
 IOUEval.external_update() after a frame.  No GPU work falls back to torch: a missing kernel is an error.
 """
@@ -351,3 +357,115 @@ class SweepEvaluator(FrameEvaluator):
                            self._ws("labels_u8", (self.n_points,), torch.uint8) if want_labels else None)
         self.views_in_sweep = 0
         return out
+
+
+def _is_dev(t, dtype, shape=None):
+    return (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()
+            and (shape is None or tuple(t.shape) == tuple(shape)))
+
+
+def range_batch_eval(prob, proj_range, offsets, px, py, unproj_range, sem=None, lut=None, label=None, knn=None,
+                     pixel_conf=None, point_conf=None, argmax_ws=None, labels=None):
+    """B range-image sweeps in one call (pmf_eval_range_batch).  prob f32[B,C,H,W]; proj_range f32[B,H,W]; the points of
+    the B sweeps concatenated: px (column) / py (row) int32[P], unproj_range f32[P], sem int32[P] raw ids, sweep b owning
+    [offsets[b], offsets[b+1]) (offsets int64[B+1] on the device); lut int32; label f32[B,H,W] with pixel_conf; knn None
+    (the label at the point's pixel) or (k, search, inv_gauss f32 device, cutoff); pixel_conf / point_conf int64[C,C]
+    to add to, or None.  -> (labels int32[P], argmax int32[B,H,W]).  All tensors contiguous on the device."""
+    if knn is not None and int(knn[1]) % 2 == 0:
+        raise ValueError("Nearest neighbor kernel must be odd number")        # knn.py:73-74
+    if not (isinstance(prob, torch.Tensor) and prob.dim() == 4 and _is_dev(prob, torch.float32)):
+        raise ValueError("prob must be a contiguous float32 CUDA tensor [B, C, H, W]")
+    B, Cn, H, W = prob.shape
+    dev = prob.device
+    if not _is_dev(offsets, torch.int64, (B + 1,)):
+        raise ValueError("offsets must be a contiguous int64 CUDA tensor [B + 1]")
+    if not (_is_dev(px, torch.int32) and px.dim() == 1 and _is_dev(py, torch.int32, px.shape)):
+        raise ValueError("px / py must be contiguous int32 CUDA tensors [P]")
+    P = int(px.shape[0])
+    if knn is not None:
+        if not (_is_dev(proj_range, torch.float32, (B, H, W)) and _is_dev(unproj_range, torch.float32, (P,))):
+            raise ValueError("the KNN vote needs proj_range float32 [B, H, W] and unproj_range float32 [P] on the device")
+        if not _is_dev(knn[2], torch.float32, (int(knn[1]) ** 2,)):
+            raise ValueError("inv_gauss must be a float32 CUDA tensor [search * search]")
+    if (label is None) != (pixel_conf is None):
+        raise ValueError("label and pixel_conf go together")
+    for name, c in (("pixel_conf", pixel_conf), ("point_conf", point_conf)):
+        if c is not None and not _is_dev(c, torch.int64, (Cn, Cn)):
+            raise ValueError("%s must be a contiguous int64 CUDA tensor [%d, %d]" % (name, Cn, Cn))
+    if label is not None and not _is_dev(label, torch.float32, (B, H, W)):
+        raise ValueError("label must be a contiguous float32 CUDA tensor [B, H, W]")
+    if point_conf is not None and not (_is_dev(sem, torch.int32, (P,)) and _is_dev(lut, torch.int32)
+                                       and lut.dim() == 1 and lut.shape[0] >= 1):
+        raise ValueError("point_conf needs sem int32 [P] and lut int32 on the device")
+    if argmax_ws is None:
+        argmax_ws = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+    elif not (_is_dev(argmax_ws, torch.int32) and argmax_ws.numel() == B * H * W):
+        raise ValueError("argmax_ws must be a contiguous int32 CUDA tensor of B * H * W elements")
+    if labels is None:
+        labels = torch.empty(P, dtype=torch.int32, device=dev)
+    elif not _is_dev(labels, torch.int32, (P,)):
+        raise ValueError("labels must be a contiguous int32 CUDA tensor [P]")
+    k_, search, inv_g, cutoff = (0, 0, None, 0.0) if knn is None else knn
+    nlut = int(lut.shape[0]) if point_conf is not None else 0
+    L.check(L.lib().pmf_eval_range_batch(
+        prob.data_ptr(), B, Cn, H, W, _ptr(label), _ptr(proj_range if knn is not None else None), offsets.data_ptr(), P,
+        px.data_ptr(), py.data_ptr(), _ptr(unproj_range if knn is not None else None),
+        _ptr(sem if point_conf is not None else None), _ptr(lut if point_conf is not None else None), nlut, int(k_),
+        int(search), _ptr(inv_g), C.c_float(float(cutoff)), argmax_ws.data_ptr(), labels.data_ptr(), _ptr(pixel_conf),
+        _ptr(point_conf), _stream(dev)), "pmf_eval_range_batch")
+    return labels, argmax_ws.view(B, H, W)
+
+
+class RangeSweepEvaluator(object):
+    """SalsaNext range images, B sweeps per forward: post() is the whole device work behind the network for a batch.
+    Owns the workspaces (grow-only, reused across batches: returned tensors are views, consume them before the next
+    batch) and the cached inverse-Gaussian window.  knn_params: post.KNN.params of the config, None = gather."""
+
+    def __init__(self, nclasses, knn_params=None, device="cuda"):
+        self.nclasses = int(nclasses)
+        self.device = torch.device(device)
+        self.knn = None
+        if knn_params is not None:
+            search = int(knn_params["search"])
+            if search % 2 == 0:
+                raise ValueError("Nearest neighbor kernel must be odd number")        # knn.py:73-74
+            w = inverse_gaussian_window(search, knn_params["sigma"]).to(self.device)
+            self.knn = (int(knn_params["knn"]), search, w, float(knn_params["cutoff"]))
+        self._buf = {}
+        self.labels = None          # int32[P] of the last batch, all its sweeps in order (what post() returns slices of)
+
+    _ws = FrameEvaluator._ws
+
+    def post(self, prob, items, pixel_conf=None, point_conf=None):
+        """prob: the network's probability maps [B, C, H, W] of the B sweeps in items; items: B dicts of the loader's
+        _eval_item (label f32[H,W], proj_range f32[H,W], px / py int32[P_b], depth f32[P_b], sem int32[P_b], lut int32);
+        pixel_conf / point_conf: int64 [C, C] device tensors to add to (or None).  The ragged point arrays are
+        concatenated with one copy per array.  -> list of B int32 label tensors (views of one workspace)."""
+        B = len(items)
+        if not (isinstance(prob, torch.Tensor) and prob.dim() == 4 and prob.shape[0] == B):
+            raise ValueError("prob must be [B, C, H, W] with one map per item")
+        if B == 0:
+            self.labels = torch.empty(0, dtype=torch.int32, device=self.device)
+            return []
+        H, W = prob.shape[2], prob.shape[3]
+        counts = [int(it["px"].shape[0]) for it in items]
+        P = sum(counts)
+        off = [0]
+        for n in counts:
+            off.append(off[-1] + n)
+        offsets = torch.tensor(off, dtype=torch.int64).to(self.device, non_blocking=True)
+        cat = lambda key, dtype: torch.cat([it[key] for it in items], out=self._ws(key, (P,), dtype))
+        px, py = cat("px", torch.int32), cat("py", torch.int32)
+        use_knn = self.knn is not None
+        depth = cat("depth", torch.float32) if use_knn else None
+        sem = cat("sem", torch.int32) if point_conf is not None else None
+        rng = torch.stack([it["proj_range"] for it in items], out=self._ws("range", (B, H, W), torch.float32)) \
+            if use_knn else None
+        label = torch.stack([it["label"] for it in items], out=self._ws("label", (B, H, W), torch.float32)) \
+            if pixel_conf is not None else None
+        labels, _ = range_batch_eval(
+            prob, rng, offsets, px, py, depth, sem=sem, lut=items[0]["lut"] if point_conf is not None else None,
+            label=label, knn=self.knn, pixel_conf=pixel_conf, point_conf=point_conf,
+            argmax_ws=self._ws("amap", (B, H, W), torch.int32), labels=self._ws("labels", (P,), torch.int32))
+        self.labels = labels
+        return [labels[off[b]:off[b + 1]] for b in range(B)]
