@@ -645,6 +645,29 @@ int pmf_eval_view_merge(const float* prob, int32_t C, int32_t H, int32_t W, int3
  * label_full[p] = 0 for the next sweep.  P == 0 is a no-op. */
 int pmf_eval_sweep_finish(float* conf_full, int32_t* label_full, int64_t P, const int32_t* sem, const int32_t* lut,
                           int32_t nlut, int32_t C, int64_t* conf, uint8_t* out_u8, pmf_stream_t s);
+/* ---- full nuScenes sweeps: camera labels filled from a LiDAR-only prediction (tasks/pmf_eval_nuscenes/testset_eval/main.py
+ * of the reference, MergePred) -------------------------------------------------------------------------------------------
+ * The rule, per point p (main_pred / sub_pred int32 labels, the camera + LiDAR model's and the LiDAR-only model's):
+ *   pred = main_pred[p] != 0 ? main_pred[p] : sub_pred[p];  source = main_pred[p] != 0 ? 0 : 1;
+ *   if (pred == 0) { pred = fill_class; source = 2; }
+ * pmf_eval_fill: P points, any number of sweeps concatenated (the rule is point-wise: one launch serves a batch of files).
+ * out_u8 (optional) uint8[P] = pred modulo 256 (numpy's astype(uint8)); conf (optional, int64[C][C], C <= 64) += (pred, gt)
+ * for EVERY point with 0 <= pred < C, gt = lut[sem[p]] (sem int32[P] raw ids, ids outside the lut -> class 0, gt 0 counts
+ * too: unlike pmf_eval_sweep_finish there is no pred != 0 gate; a gt outside [0, C) is not counted); counts (optional)
+ * int64[3] += the number of points by source: from main_pred / from sub_pred / filled.  sem and lut are needed only with
+ * conf.  P == 0 is a no-op. */
+int pmf_eval_fill(const int32_t* main_pred, const int32_t* sub_pred, int64_t P, int32_t fill_class, const int32_t* sem,
+                  const int32_t* lut, int32_t nlut, int32_t C, int64_t* conf, int64_t* counts, uint8_t* out_u8,
+                  pmf_stream_t s);
+/* pmf_eval_sweep_finish_fill: the online form, one pass over the sweep after its last view.  Everything
+ * pmf_eval_sweep_finish does, bit-identically: conf_cam (optional) += the camera-only confusion with its pred != 0 gate,
+ * out_cam_u8 (optional) uint8[P] = label_full, conf_full / label_full zeroed.  In the same pass the rule above with
+ * main_pred = label_full[p] and sub_pred int32[P]: conf_fused (optional), counts (optional, int64[3]) and out_u8 (optional,
+ * uint8[P]) exactly as pmf_eval_fill(label_full, sub_pred, ...) would give them.  sem and lut are needed with either
+ * confusion.  C <= 64.  P == 0 is a no-op. */
+int pmf_eval_sweep_finish_fill(float* conf_full, int32_t* label_full, int64_t P, const int32_t* sub_pred, int32_t fill_class,
+                               const int32_t* sem, const int32_t* lut, int32_t nlut, int32_t C, int64_t* conf_cam,
+                               int64_t* conf_fused, int64_t* counts, uint8_t* out_cam_u8, uint8_t* out_u8, pmf_stream_t s);
 /* ---- SalsaNext evaluation on range images, B sweeps per call (tasks/salsanext_eval_nuscenes/infer.py:90-119) -----------
  * Every sweep has the same H x W (sensor.proj_h x proj_w), so the maps of a forward are one batch; the points of the B sweeps
  * are concatenated, sweep b owning [offsets[b], offsets[b + 1]) (offsets int64[B + 1] on the device, offsets[B] == P_total).

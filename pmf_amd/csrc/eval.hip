@@ -7,6 +7,7 @@
 //   pmf_eval_points  labels of the K kept points: a gather of the argmax straight from the probability window, or the
 //                    KNN vote of knn.hip on the int32 map; += [C][C] point confusion, optional uint32 inverse-mapped ids
 //   pmf_eval_range_batch  SalsaNext range images (every sweep 32x2048 on nuScenes), B sweeps per call: section (e)
+//   pmf_eval_fill / pmf_eval_sweep_finish_fill  full sweeps: camera labels filled from a LiDAR-only prediction: section (f)
 // Ties of the argmax go to the lowest class and a NaN wins (torch.argmax).  Confusion counts are per-workgroup LDS
 // histograms flushed with 64-bit global atomics (as loss.hip's fused loss does); all stores are vector stores.
 #include "common.h"
@@ -345,6 +346,131 @@ extern "C" int pmf_eval_sweep_finish(float* conf_full, int32_t* label_full, int6
   const int64_t g = cdiv64(P, 256);
   hipLaunchKernelGGL(eval_sweep_finish_k, dim3((unsigned)(g < EV_GRID ? g : EV_GRID)), dim3(256), 0, (hipStream_t)s,
                      conf_full, label_full, P, sem, lut, nlut, C, (unsigned long long*)conf, out_u8);
+  PMF_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- (f) full sweeps: the camera labels filled from a LiDAR-only prediction ---------------------------------------------
+// (tasks/pmf_eval_nuscenes/testset_eval/main.py of the reference, MergePred: where the camera model said 0 the LiDAR-only
+// label is taken, what is still 0 becomes one fixed class, and ALL points are scored: no pred != 0 gate on the ground
+// truth.)  ev_fill_point is the one statement of that rule; the batched pass and the online sweep finish both call it.
+// n[3] are the lane's running counts by source: taken from the main prediction / from the sub prediction / filled.
+__device__ __forceinline__ void ev_fill_point(int main_pred, int sub_pred, int fill_class, int64_t p,
+                                              const int32_t* __restrict__ sem,
+                                              const int32_t* __restrict__ lut, int nlut, int C, unsigned* hist,
+                                              uint8_t* __restrict__ out_u8, unsigned (&n)[3]) {
+  int pred = main_pred != 0 ? main_pred : sub_pred;
+  int source = main_pred != 0 ? 0 : 1;
+  if (pred == 0) { pred = fill_class; source = 2; }
+  if (out_u8) out_u8[p] = (uint8_t)pred;                 // modulo 256, as numpy's astype(uint8)
+  if (hist) {
+    const int sl = sem[p];
+    const int t = (sl >= 0 && sl < nlut) ? lut[sl] : 0;
+    if (t >= 0 && t < C && pred >= 0 && pred < C) atomicAdd(&hist[pred * C + t], 1u);
+  }
+  n[0] += source == 0;
+  n[1] += source == 1;
+  n[2] += source == 2;
+}
+
+// The workgroup's three source counts: a shuffle reduction per wave, one LDS slot per wave, then one 64-bit atomic per
+// count and workgroup.  Every lane of the workgroup calls it (it holds a barrier).
+__device__ __forceinline__ void ev_counts_flush(const unsigned (&n)[3], unsigned (*wave_n)[3], unsigned long long* counts) {
+  unsigned v[3] = {n[0], n[1], n[2]};
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+    for (int d = 32; d >= 1; d >>= 1) v[k] += __shfl_down(v[k], d, 64);
+  if ((threadIdx.x & 63) == 0)
+    for (int k = 0; k < 3; ++k) wave_n[threadIdx.x >> 6][k] = v[k];
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    unsigned long long t = 0;
+    for (int wv = 0; wv < (int)(blockDim.x >> 6); ++wv) t += wave_n[wv][threadIdx.x];
+    if (t) atomicAdd(counts + threadIdx.x, t);
+  }
+}
+
+// One lane per point of the concatenated sweeps: two coalesced int32 reads, one byte out.
+__global__ __launch_bounds__(256) void eval_fill_k(const int32_t* __restrict__ main_pred,
+                                                   const int32_t* __restrict__ sub_pred, int64_t P, int fill_class,
+                                                   const int32_t* __restrict__ sem,
+                                                   const int32_t* __restrict__ lut, int nlut, int C,
+                                                   unsigned long long* __restrict__ conf,
+                                                   unsigned long long* __restrict__ counts, uint8_t* __restrict__ out_u8) {
+  __shared__ unsigned hist[EV_MAXC * EV_MAXC];
+  __shared__ unsigned wave_n[4][3];
+  if (conf) ev_hist_zero(hist, C);
+  unsigned n[3] = {0u, 0u, 0u};
+  for (int64_t p = blockIdx.x * (int64_t)256 + threadIdx.x; p < P; p += (int64_t)gridDim.x * 256)
+    ev_fill_point(main_pred[p], sub_pred[p], fill_class, p, sem, lut, nlut, C, conf ? hist : nullptr, out_u8, n);
+  if (conf) ev_hist_flush(hist, C, conf);
+  if (counts) ev_counts_flush(n, wave_n, counts);
+}
+
+extern "C" int pmf_eval_fill(const int32_t* main_pred, const int32_t* sub_pred, int64_t P, int32_t fill_class,
+                             const int32_t* sem, const int32_t* lut, int32_t nlut, int32_t C, int64_t* conf,
+                             int64_t* counts, uint8_t* out_u8, pmf_stream_t s) {
+  if (P < 0 || C < 1 || C > EV_MAXC) return PMF_E_ARG;
+  if (P == 0) return 0;
+  if (!main_pred || !sub_pred) return PMF_E_ARG;
+  if (conf && (!sem || !lut || nlut < 1)) return PMF_E_ARG;
+  if (!conf && !counts && !out_u8) return 0;
+  const int64_t g = cdiv64(P, 256);
+  hipLaunchKernelGGL(eval_fill_k, dim3((unsigned)(g < EV_GRID ? g : EV_GRID)), dim3(256), 0, (hipStream_t)s, main_pred,
+                     sub_pred, P, fill_class, sem, lut, nlut, C, (unsigned long long*)conf, (unsigned long long*)counts,
+                     out_u8);
+  PMF_LAUNCH_CHECK();
+  return 0;
+}
+
+// eval_sweep_finish_k and the fill in one pass over the sweep: the camera-only count keeps its pred != 0 gate and its own
+// histogram, the fused count and labels come from ev_fill_point with main_pred = the merged camera label; the state is
+// read once and zeroed.  The extra traffic over the plain finish is one int32 read (sub_pred[p]) per point.
+__global__ __launch_bounds__(256) void eval_sweep_finish_fill_k(float* __restrict__ conf_full,
+                                                                int32_t* __restrict__ label_full,
+                                                                int64_t P, const int32_t* __restrict__ sub_pred,
+                                                                int fill_class, const int32_t* __restrict__ sem,
+                                                                const int32_t* __restrict__ lut, int nlut, int C,
+                                                                unsigned long long* __restrict__ conf_cam,
+                                                                unsigned long long* __restrict__ conf_fused,
+                                                                unsigned long long* __restrict__ counts,
+                                                                uint8_t* __restrict__ out_cam_u8,
+                                                                uint8_t* __restrict__ out_u8) {
+  __shared__ unsigned hist_cam[EV_MAXC * EV_MAXC];
+  __shared__ unsigned hist[EV_MAXC * EV_MAXC];
+  __shared__ unsigned wave_n[4][3];
+  if (conf_cam) ev_hist_zero(hist_cam, C);
+  if (conf_fused) ev_hist_zero(hist, C);
+  unsigned n[3] = {0u, 0u, 0u};
+  for (int64_t p = blockIdx.x * (int64_t)256 + threadIdx.x; p < P; p += (int64_t)gridDim.x * 256) {
+    const int pred = label_full[p];
+    if (conf_cam) {
+      const int sl = sem[p];
+      const int t = (pred != 0 && sl >= 0 && sl < nlut) ? lut[sl] : 0;
+      if (t >= 0 && t < C && pred >= 0 && pred < C) atomicAdd(&hist_cam[pred * C + t], 1u);
+    }
+    if (out_cam_u8) out_cam_u8[p] = (uint8_t)pred;
+    ev_fill_point(pred, sub_pred[p], fill_class, p, sem, lut, nlut, C, conf_fused ? hist : nullptr, out_u8, n);
+    conf_full[p] = 0.f;
+    label_full[p] = 0;
+  }
+  if (conf_cam) ev_hist_flush(hist_cam, C, conf_cam);
+  if (conf_fused) ev_hist_flush(hist, C, conf_fused);
+  if (counts) ev_counts_flush(n, wave_n, counts);
+}
+
+extern "C" int pmf_eval_sweep_finish_fill(float* conf_full, int32_t* label_full, int64_t P, const int32_t* sub_pred,
+                                          int32_t fill_class, const int32_t* sem, const int32_t* lut, int32_t nlut,
+                                          int32_t C, int64_t* conf_cam, int64_t* conf_fused, int64_t* counts,
+                                          uint8_t* out_cam_u8, uint8_t* out_u8, pmf_stream_t s) {
+  if (P < 0 || C < 1 || C > EV_MAXC) return PMF_E_ARG;
+  if (P == 0) return 0;
+  if (!conf_full || !label_full || !sub_pred) return PMF_E_ARG;
+  if ((conf_cam || conf_fused) && (!sem || !lut || nlut < 1)) return PMF_E_ARG;
+  const int64_t g = cdiv64(P, 256);
+  hipLaunchKernelGGL(eval_sweep_finish_fill_k, dim3((unsigned)(g < EV_GRID ? g : EV_GRID)), dim3(256), 0, (hipStream_t)s,
+                     conf_full, label_full, P, sub_pred, fill_class, sem, lut, nlut, C, (unsigned long long*)conf_cam,
+                     (unsigned long long*)conf_fused, (unsigned long long*)counts, out_cam_u8, out_u8);
   PMF_LAUNCH_CHECK();
   return 0;
 }

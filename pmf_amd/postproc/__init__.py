@@ -1,4 +1,4 @@
 from .knn import KNN  # noqa: F401
 from .merge import getMergePred  # noqa: F401
 from .frame_eval import (FrameEvaluator, SweepEvaluator, RangeSweepEvaluator, range_batch_eval, pad_geometry,  # noqa: F401
-                         pad_geometry_bottom)
+                         pad_geometry_bottom, fill_labels, sweep_finish_fill)

@@ -21,6 +21,13 @@ through the network per forward and everything behind it is one batched pass -- 
   range   argmax of the B maps, += pixel confusion; per point the label at its pixel or the KNN vote, int32 labels,
           += point confusion: two launches per batch                                          (pmf_eval_range_batch)
 
+Full nuScenes sweeps (tasks/pmf_eval_nuscenes/testset_eval/main.py, MergePred): the camera + LiDAR labels cover the points
+some camera sees, a LiDAR-only prediction fills the rest, what is still 0 becomes one class, and all points are scored:
+
+  fill    per point main != 0 ? main : sub, 0 -> fill_class; uint8 labels, += confusion over ALL points, += the three
+          source counts; any number of sweeps concatenated                                    (pmf_eval_fill)
+  finish  with a fallback: the plain finish and the fill in one pass over the sweep's state    (pmf_eval_sweep_finish_fill)
+
 The confusion matrices are IOUEval.conf_matrix tensors (int64, on the device) updated in place; call
 IOUEval.external_update() after a frame.  No GPU work falls back to torch: a missing kernel is an error.
 """
@@ -281,6 +288,68 @@ def sweep_finish(conf_full, label_full, nclasses, sem=None, lut=None, conf=None,
     return out_u8
 
 
+def _check_conf(name, conf, nclasses):
+    if conf is not None and not (isinstance(conf, torch.Tensor) and conf.is_cuda and conf.dtype == torch.int64
+                                 and conf.is_contiguous() and tuple(conf.shape) == (nclasses, nclasses)):
+        raise ValueError("%s must be a contiguous int64 CUDA tensor [%d, %d]" % (name, nclasses, nclasses))
+
+
+def _check_fill(P, nclasses, sem, lut, need_gt, counts, out_u8):
+    """the optional arguments the two fill entry points share -> (sem, lut) or (None, None) without a confusion"""
+    if not 1 <= int(nclasses) <= 64:
+        raise ValueError("nclasses must be in 1..64, got %r" % (nclasses,))
+    if need_gt:
+        if not (_is_dev(sem, torch.int32) and _is_dev(lut, torch.int32) and sem.dim() == 1 and lut.dim() == 1
+                and sem.shape[0] == P and lut.shape[0] >= 1):
+            raise ValueError("a confusion needs sem int32[%d] and lut int32 on the device" % P)
+    else:
+        sem = lut = None
+    if counts is not None and not _is_dev(counts, torch.int64, (3,)):
+        raise ValueError("counts must be a contiguous int64 CUDA tensor [3]")
+    if out_u8 is not None and not _is_dev(out_u8, torch.uint8, (P,)):
+        raise ValueError("out_u8 must be a contiguous uint8 CUDA tensor [%d]" % P)
+    return sem, lut
+
+
+def fill_labels(main, sub, nclasses, fill_class=11, sem=None, lut=None, conf=None, counts=None, out_u8=None):
+    """the reference's MergePred rule on the device (pmf_eval_fill), for P points = any number of sweeps concatenated: main /
+    sub int32[P] (the camera + LiDAR labels, 0 where no camera saw the point, and the LiDAR-only labels): pred = main where
+    non-zero, else sub, else fill_class.  out_u8 uint8[P] = pred (numpy's astype(uint8)); conf int64[C,C] += (pred,
+    lut[sem]) over ALL points (sem int32[P] raw ids, lut int32); counts int64[3] += points taken from main / from sub /
+    filled.  Each output is optional.  -> out_u8."""
+    if not (_is_dev(main, torch.int32) and main.dim() == 1):
+        raise ValueError("main must be a contiguous int32 CUDA tensor [P]")
+    P = int(main.shape[0])
+    if not _is_dev(sub, torch.int32, (P,)):
+        raise ValueError("sub must be a contiguous int32 CUDA tensor [%d], one label per point of main" % P)
+    _check_conf("conf", conf, nclasses)
+    sem, lut = _check_fill(P, nclasses, sem, lut, conf is not None, counts, out_u8)
+    L.check(L.lib().pmf_eval_fill(
+        main.data_ptr(), sub.data_ptr(), P, int(fill_class), _ptr(sem), _ptr(lut), 0 if lut is None else int(lut.shape[0]),
+        int(nclasses), _ptr(conf), _ptr(counts), _ptr(out_u8), _stream(main.device)), "pmf_eval_fill")
+    return out_u8
+
+
+def sweep_finish_fill(conf_full, label_full, sub, nclasses, fill_class=11, sem=None, lut=None, conf=None, fused_conf=None,
+                      counts=None, out_cam_u8=None, out_u8=None):
+    """sweep_finish and fill_labels(label_full, sub) in one pass over the state (pmf_eval_sweep_finish_fill): conf /
+    out_cam_u8 as sweep_finish gives them (camera-only, scored where the label is non-zero), fused_conf / counts / out_u8 as
+    fill_labels gives them, and the state back to zero.  -> out_u8."""
+    P = _check_state(conf_full, label_full)
+    if not _is_dev(sub, torch.int32, (P,)):
+        raise ValueError("sub must be a contiguous int32 CUDA tensor [%d], one label per point of the sweep" % P)
+    _check_conf("conf", conf, nclasses)
+    _check_conf("fused_conf", fused_conf, nclasses)
+    sem, lut = _check_fill(P, nclasses, sem, lut, conf is not None or fused_conf is not None, counts, out_u8)
+    if out_cam_u8 is not None and not _is_dev(out_cam_u8, torch.uint8, (P,)):
+        raise ValueError("out_cam_u8 must be a contiguous uint8 CUDA tensor [%d]" % P)
+    L.check(L.lib().pmf_eval_sweep_finish_fill(
+        conf_full.data_ptr(), label_full.data_ptr(), P, sub.data_ptr(), int(fill_class), _ptr(sem), _ptr(lut),
+        0 if lut is None else int(lut.shape[0]), int(nclasses), _ptr(conf), _ptr(fused_conf), _ptr(counts),
+        _ptr(out_cam_u8), _ptr(out_u8), _stream(conf_full.device)), "pmf_eval_sweep_finish_fill")
+    return out_u8
+
+
 class SweepEvaluator(FrameEvaluator):
     """nuScenes: the views of one sweep at a time.  pre() / post_view() per view, finish() after the last one; the
     running (confidence, label) state of the sweep lives on the device, sized to the largest sweep seen, zero between
@@ -345,16 +414,26 @@ class SweepEvaluator(FrameEvaluator):
                    conf_ws=self._ws("cmap", (h * w,), torch.int32) if use_knn else None)
         self.views_in_sweep += 1
 
-    def finish(self, sem, lut, n_points, point_conf=None, want_labels=True):
+    def finish(self, sem, lut, n_points, point_conf=None, want_labels=True, fallback=None, fill_class=11, fused_conf=None,
+               counts=None):
         """after the last view of the sweep: point_conf int64[C,C] += the sweep's point confusion (sem int32[P] raw ids, lut
-        int32), -> uint8[P] labels (None unless want_labels); the state is zero again."""
+        int32), -> uint8[P] labels (None unless want_labels); the state is zero again.
+        fallback int32[P] (a LiDAR-only prediction of the same sweep): the same pass also fills the points no camera
+        labelled (fill_labels' rule), fused_conf int64[C,C] += the confusion over ALL points, counts int64[3] += the source
+        counts, and the labels returned are the FUSED uint8 labels."""
         if self.views_in_sweep == 0:
             raise RuntimeError("finish() without a view")
         if int(n_points) != self.n_points:
             raise RuntimeError("finish() for %d points, the sweep's views carried %d" % (int(n_points), self.n_points))
         conf_full, label_full = self._state(self.n_points)
-        out = sweep_finish(conf_full, label_full, self.nclasses, sem, lut, point_conf,
-                           self._ws("labels_u8", (self.n_points,), torch.uint8) if want_labels else None)
+        out = self._ws("labels_u8", (self.n_points,), torch.uint8) if want_labels else None
+        if fallback is None:
+            if fused_conf is not None or counts is not None:
+                raise ValueError("fused_conf / counts need a fallback prediction")
+            out = sweep_finish(conf_full, label_full, self.nclasses, sem, lut, point_conf, out)
+        else:
+            out = sweep_finish_fill(conf_full, label_full, fallback, self.nclasses, fill_class, sem, lut, point_conf,
+                                    fused_conf, counts, None, out)
         self.views_in_sweep = 0
         return out
 

@@ -12,10 +12,18 @@ point-wise and pixel-wise mean / per-class IoU, Acc and Recall, the LaTeX row, c
 confusion / Acc / Recall matrices.  The dataset object is the devkit's business (pc_processor.dataset.nuScenes.NuscenesV2);
 any object with its attributes can be passed in: Experiment(settings, dataset=...).
 
+With the optional key sub_pred_folder (a folder written by tasks/salsanext_eval_nuscenes: preds/lidarseg/<val|test>/
+<lidar_token>_lidarseg.bin, sub_pred_dtype int32 by default) the sweep's LiDAR-only labels are read and uploaded, and the
+finish becomes pmf_eval_sweep_finish_fill: the same pass also fills the points no camera labelled (the rule of
+tasks/pmf_eval_nuscenes/testset_eval: camera label where non-zero, else the LiDAR-only label, else fill_class), scores ALL
+points into a second confusion, and the file written is the FUSED uint8 sweep, with preds/<val|test>/submission.json next to
+it.  The camera-only report is unchanged; a "Fused point-wise" block and the share of points by source follow it.
+
     python infer.py config_server_nus.yaml [--dump-probs DIR]
 """
 import argparse
 import datetime
+import json
 import os
 import sys
 import time
@@ -62,8 +70,24 @@ class Inference(object):
         self.evaluator = pc_processor.metrics.IOUEval(n_classes=settings.n_classes, device=dev, ignore=[0])
         self.pixel_eval = pc_processor.metrics.IOUEval(n_classes=settings.n_classes, device=dev, ignore=[0])
         self.data_split = "val" if settings.has_label else "test"
+        # with sub_pred_folder: the fused full-sweep confusion and the points by source (main / sub / filled)
+        self.fused_eval = self.source_counts = None
+        if getattr(settings, "sub_pred_folder", None) is not None:
+            self.fused_eval = pc_processor.metrics.IOUEval(n_classes=settings.n_classes, device=dev, ignore=[0])
+            self.source_counts = torch.zeros(3, dtype=torch.int64, device=dev)
         if self.knn_flag:
             self.recorder.logger.info("using KNN Post Process")
+
+    def _fallback(self, token, n_points):
+        """the sweep's LiDAR-only labels from sub_pred_folder -> int32[P] on the device"""
+        s = self.settings
+        path = os.path.join(s.sub_pred_folder, "preds", "lidarseg", self.data_split, "{}_lidarseg.bin".format(token))
+        if not os.path.isfile(path):
+            raise FileNotFoundError("no sub prediction for sweep {}: {}".format(token, path))
+        sub = np.fromfile(path, dtype=np.dtype(s.sub_pred_dtype)).astype(np.int32, copy=False)
+        if sub.shape[0] != n_points:
+            raise ValueError("sweep {}: {} points, the sub prediction has {}".format(token, n_points, sub.shape[0]))
+        return torch.from_numpy(sub).cuda()
 
     def _initDataloader(self, dataset):
         s = self.settings
@@ -88,6 +112,10 @@ class Inference(object):
         self.model.eval()
         self.evaluator.reset()
         self.pixel_eval.reset()
+        fuse = self.fused_eval is not None
+        if fuse:
+            self.fused_eval.reset()
+            self.source_counts.zero_()
         ds = self.pv_loader.dataset
         shapes, written = {}, {}
         n = len(self.pv_loader)
@@ -122,11 +150,19 @@ class Inference(object):
                 token = current
             assert current == token, "views of different sweeps inside one group of six: {} / {}".format(token, current)
             if self.sweep_eval.views_in_sweep == N_CAM:
+                extra_kw = {}
+                if fuse:
+                    extra_kw = dict(fallback=self._fallback(token, int(extra["sem"].shape[0])), fill_class=s.fill_class,
+                                    fused_conf=self.fused_eval.conf_matrix if s.has_label else None,
+                                    counts=self.source_counts)
                 labels = self.sweep_eval.finish(
                     extra["sem"], extra["lut"], extra["sem"].shape[0],
-                    point_conf=self.evaluator.conf_matrix if s.has_label else None, want_labels=s.save_pred_results)
+                    point_conf=self.evaluator.conf_matrix if s.has_label else None, want_labels=s.save_pred_results,
+                    **extra_kw)
                 if s.has_label:
                     self.evaluator.external_update()
+                    if fuse:
+                        self.fused_eval.external_update()
                 if s.save_pred_results:
                     out_dir = os.path.join(self.prediction_path, "lidarseg", self.data_split)
                     os.makedirs(out_dir, exist_ok=True)
@@ -151,6 +187,19 @@ class Inference(object):
         if s.has_label:
             self.report("Point-wise Evaluation Results (3D eval)", self.evaluator, pointwise=True)
             self.report("Pixel-wise Evaluation Results (2D eval)", self.pixel_eval, pointwise=False)
+        if fuse:
+            if s.has_label:
+                self.report("Fused point-wise Evaluation Results (3D eval, all points)", self.fused_eval, pointwise=True)
+            c = self.source_counts.cpu().tolist()
+            t = max(sum(c), 1)
+            log("Label source: main {:.4f} ({}), sub {:.4f} ({}), filled {:.4f} ({}) of {} points".format(
+                c[0] / t, c[0], c[1] / t, c[1], c[2] / t, c[2], sum(c)))
+            if s.save_pred_results:
+                json_dir = os.path.join(self.prediction_path, self.data_split)
+                os.makedirs(json_dir, exist_ok=True)
+                with open(os.path.join(json_dir, "submission.json"), "w") as f:
+                    json.dump({"meta": {"use_camera": True, "use_lidar": True, "use_radar": False, "use_map": False,
+                                        "use_external": False}}, f, ensure_ascii=False, indent=4)
         return written
 
     def report(self, title, ev, pointwise):

@@ -1,6 +1,8 @@
 """Options of the EPMF nuScenes evaluation task (tasks/epmf_eval_nuscenes/option.py of the reference): yaml keys ->
 attributes.  The results go to <pretrained_path>/Eval-<dataset>-PMFNet-<best_model.strip(".pth")>-<KNN-search|noKNN>-
-<experiment_id>, created without the reference's interactive delete / quit prompt (an existing directory is reused)."""
+<experiment_id>, created without the reference's interactive delete / quit prompt (an existing directory is reused).
+Optional keys beyond the reference's: sub_pred_folder (+ sub_pred_dtype "int32" / "uint8", fill_class 11) -- with it the
+sweeps are completed from that LiDAR-only prediction folder as they finish (infer.py)."""
 import os
 
 import yaml
@@ -33,12 +35,20 @@ class Option(object):
         self.imagenet_pretrained = c.get("imagenet_pretrained", False)
         # checkpoint
         self.pretrained_model = os.path.join(c["pretrained_path"], "checkpoint", c["best_model"])
+        # optional: a LiDAR-only prediction folder (tasks/salsanext_eval_nuscenes) to fill the points no camera sees
+        self.sub_pred_folder = c.get("sub_pred_folder")
+        self.sub_pred_dtype = c.get("sub_pred_dtype", "int32")
+        self.fill_class = int(c.get("fill_class", 11))
         self._prepare()
 
     def _prepare(self):
         if not os.path.isdir(self.save_path):
             raise ValueError("pretrained model is required, please train your model first. Path not exist: {}".format(
                 self.save_path))
+        if self.sub_pred_folder is not None and not os.path.isdir(self.sub_pred_folder):
+            raise FileNotFoundError("sub prediction folder not found: {}".format(self.sub_pred_folder))
+        if self.sub_pred_dtype not in ("int32", "uint8"):
+            raise ValueError("sub_pred_dtype must be int32 or uint8, got {!r}".format(self.sub_pred_dtype))
         knn = self.config["post"]["KNN"]
         knn_str = "KNN-{}".format(knn["params"]["search"]) if knn["use"] else "noKNN"
         # (str.strip removes a character SET from both ends -- kept as the reference writes it)
