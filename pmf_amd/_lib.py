@@ -249,6 +249,42 @@ def lib():
         [C.c_void_p] * 8
     L.pmf_fill.restype = C.c_int
     L.pmf_fill.argtypes = [C.c_void_p, C.c_float, C.c_int64, C.c_void_p]
+    # csrc/elementwise.hip: p = pointer, i = int32, q = int64, v = const pmf_view_t*; every signature ends with the stream
+    p, i, q, v = C.c_void_p, C.c_int32, C.c_int64, C.POINTER(View)
+    for name, args in (
+            ("pmf_add_act", [v, v, i, p, i, q, i, i]),
+            ("pmf_add_act_bwd", [p, i, p, i, i, p, i, i, p, i, i, q, i]),
+            ("pmf_act_bwd", [p, i, p, i, i, p, i, q, i]),
+            ("pmf_colsum", [p, i, q, i, p, i]),
+            ("pmf_colsum_rows", [p, i, q, i, p, i, p]),
+            ("pmf_global_mean", [v, i, i, i, p]),
+            ("pmf_global_mean_bwd", [p, i, i, i, p, i, p, i, i]),
+            ("pmf_avgpool3s2", [v, i, i, i, i, p, i]),
+            ("pmf_avgpool3s2_bwd", [p, i, i, i, i, i, p, i, p, i, i]),
+            ("pmf_maxpool3s2", [v, i, i, i, i, p, i, p]),
+            ("pmf_maxpool3s2_bwd", [p, i, p, i, i, i, i, v, p, i, i]),
+            ("pmf_bilinear2x", [v, i, i, i, i, p, i]),
+            ("pmf_bilinear2x_bwd", [p, i, i, i, i, i, p, i, i]),
+            ("pmf_pixel_shuffle2", [v, i, i, i, i, p, i, p, i]),
+            ("pmf_pixel_shuffle2_bwd", [p, i, i, i, i, i, p, i, p, i, p, i, i]),
+            ("pmf_fusion_gate", [v, v, p, i, p, i, q, i]),
+            ("pmf_fusion_gate_bwd", [p, i, v, v, p, i, i, p, i, p, i, i, q, i]),
+            ("pmf_softmax_nhwc_to_nchw", [p, i, i, i, i, p]),
+            ("pmf_logits_nhwc_to_nchw", [p, i, i, i, i, p]),
+            ("pmf_softmax_bwd_nchw_to_nhwc", [p, p, i, i, i, p, i]),
+            ("pmf_logits_bwd_nchw_to_nhwc", [p, i, i, i, p, i]),
+            ("pmf_broadcast_rows", [p, i, i, q, i, p, i]),
+            ("pmf_nchw_to_nhwc", [p, q, q, i, i, i, p, i]),
+            ("pmf_pmask_from", [v, q, i, i, p]),
+            ("pmf_pmask_pool", [p, i, i, i, i, i, i, i, i, p, i, i]),
+            ("pmf_pmask_mul", [v, p, q, i, i, p, i]),
+            ("pmf_pmask_mul_bwd", [p, i, p, q, i, p, i, i]),
+            ("pmf_vec_add", [p, p, p, i])):
+        fn = getattr(L, name)
+        fn.restype = C.c_int
+        fn.argtypes = args + [p]
+    L.pmf_debug_col.restype = C.c_int
+    L.pmf_debug_col.argtypes = [C.c_int32, C.c_int32]
     L.pmf_eval_pre.restype = C.c_int
     L.pmf_eval_pre.argtypes = [C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p] * 6
     L.pmf_eval_argmax.restype = C.c_int

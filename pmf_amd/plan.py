@@ -313,10 +313,23 @@ class Plan(PlanConvMixin, PlanTuneMixin, PlanRunMixin):
         self.emit(lst, L.OP_FILL, f)
 
     # ---- element-wise primitives -----------------------------------------------------------------
+    def _no_relu_view(self, op, *views):
+        """only maxpool3s2_bwd (and the conv input-gradient epilogue) applies the relu' mask of a relu=True view: the other
+        backward kernels deliver dL/d(view output), which is not the gradient of what is under the ReLU.
+        Each primitive calls this exactly where it registers a backward: add_act, pmask_mul and avgpool register one only for an
+        operand with needs_grad, so they pass only those; bilinear, pixel_shuffle, gate and global_mean register theirs for
+        every operand in training mode (grad_of allocates the gradient either way), so they refuse every relu view."""
+        for v in views:
+            if v is not None and v.relu:
+                raise NotImplementedError("%s: the backward kernel does not apply the relu' mask of the relu view of %s"
+                                          % (op, v.t.name or "<unnamed>"))
+
     def add_act(self, a, b, act, name=""):
         t = a.t
         if self.training and (a.cmul is not None or (b is not None and b.cmul is not None)):
             raise NotImplementedError("add_act: (n,c) multipliers on residual operands have no backward here")
+        if self.training:
+            self._no_relu_view("add_act", a if a.t.needs_grad else None, b if (b is not None and b.t.needs_grad) else None)
         out = T(self, t.N, t.H, t.W, t.C, name)
 
         def f(op):
@@ -397,6 +410,7 @@ class Plan(PlanConvMixin, PlanTuneMixin, PlanRunMixin):
         if self.training and t.needs_grad:
             if v.cmul is not None:
                 raise NotImplementedError("pmask_mul: (n,c) multiplier on the operand has no backward here")
+            self._no_relu_view("pmask_mul", v)
 
             def backward():
                 g = self.tgrad(out)
@@ -430,6 +444,9 @@ class Plan(PlanConvMixin, PlanTuneMixin, PlanRunMixin):
         out.pool_idx, out.pool_of = idx, v  # (debug: argmax positions 0..8 as uint8 [N, OH, OW, round4(C)])
         self.note_bytes(self.fwd, "pool", 4.0 * t.C * (t.npix + out.npix) + (out.npix * t.C if with_idx else 0))
         if self.training and t.needs_grad:
+            if not with_idx:
+                self._no_relu_view("avgpool", v)
+
             def backward():
                 g = self.tgrad(out)
                 gin, acc = self.grad_of(v)
@@ -469,6 +486,8 @@ class Plan(PlanConvMixin, PlanTuneMixin, PlanRunMixin):
         self.emit(self.fwd, L.OP_BILINEAR, f)
         self.note_bytes(self.fwd, "bilinear", 4.0 * t.C * (t.npix + out.npix))
         if self.training:
+            self._no_relu_view("bilinear", v)
+
             def backward():
                 g = self.tgrad(out)
                 gin, acc = self.grad_of(v)
@@ -497,6 +516,8 @@ class Plan(PlanConvMixin, PlanTuneMixin, PlanRunMixin):
         self.emit(self.fwd, L.OP_PSHUFFLE, f)
         self.note_bytes(self.fwd, "pixel_shuffle", 8.0 * t.C * t.npix)
         if self.training:
+            self._no_relu_view("pixel_shuffle", v)
+
             def backward():
                 g = self.tgrad(out)
                 gin, acc = self.grad_of(v)
@@ -528,10 +549,15 @@ class Plan(PlanConvMixin, PlanTuneMixin, PlanRunMixin):
         self.emit(self.fwd, L.OP_GATE, f)
         self.note_bytes(self.fwd, "fusion_gate", 16.0 * t.C * t.npix)
         if self.training:
+            self._no_relu_view("gate", f_v, att_v)
+
             def backward():
                 g = self.tgrad(out)
                 gf, accf = self.grad_of(f_v)
-                gatt, _ = self.grad_of(att_v)
+                gatt, accatt = self.grad_of(att_v)
+                if accatt:
+                    raise NotImplementedError("gate: the gate backward overwrites the gradient of att, and %s already holds "
+                                              "the gradient of another consumer of %s" % (gatt.name, att_v.t.name))
                 gp, accp = self.grad_of(V(pcd))
 
                 def fb(op):
@@ -559,6 +585,8 @@ class Plan(PlanConvMixin, PlanTuneMixin, PlanRunMixin):
             s.i[0], s.i[1], s.i[2] = t.N, t.H * t.W, _ru(t.C, 4)
         self.emit(self.fwd, L.OP_GMEAN, f)
         if self.training:
+            self._no_relu_view("global_mean", v)
+
             def backward():
                 g = self.tgrad(out)
                 gin, acc = self.grad_of(v)

@@ -368,32 +368,42 @@ def _set_affine(P, aff):
         bh.tensor((sh.numel(),)).copy_(sh.to(DEV))
 
 
-def test_elementwise_primitives_fwd_bwd():
-    N, C, H, W = 2, 32, 12, 20
-    Hn = Harness([(N, C, H, W), (N, C, H, W), (N, C, H, W)], masks=4 * N * C)
+@pytest.mark.parametrize("N,C,H,W", [(2, 32, 12, 20), (3, 24, 5, 9)])
+def test_elementwise_primitives_fwd_bwd(N, C, H, W):
+    """every primitive on input tensors of its own (no two consumers share a gradient buffer), every input gradient checked.
+    A view with a constant affine (no BatchNorm behind it) receives dL/dy of the VIEW: the reference is the retained gradient
+    of the float64 view output."""
+    names = ["add.a", "add.b", "pool", "bil", "ps", "gate.f", "gate.att", "gate.pcd", "gm", "mp"]
+    Hn = Harness([(N, C, H, W)] * len(names), masks=4 * N * C)
     P = Hn.P
-    a, b, c = Hn.inputs
+    t = dict(zip(names, Hn.inputs))
     cm = (det_tensor("ew.cm", (N, C)) > -0.5).float() * 1.25
     cm2 = (det_tensor("ew.cm2", (N, C // 4)) > -0.5).float() * 1.25
     P.masks[:N * C].copy_(cm.reshape(-1).to(DEV))
     P.masks[N * C:N * C + N * C // 4].copy_(cm2.reshape(-1).to(DEV))
-    va, aff_a = _affine_view(P, a, "ew.a", C)
-    vb, aff_b = _affine_view(P, b, "ew.b", C)
-    o_add = P.add_act(va, V(c), L.ACT_RELU, name="add")
-    o_pool = P.avgpool(V(a).with_cmul(0, C), name="pool")
-    o_bil = P.bilinear(vb, name="bil")
-    o_ps = P.pixel_shuffle(V(c).with_cmul(0, C), N * C, C // 4, name="ps")
-    o_gate = P.gate(va, vb, c, name="gate")
-    o_gm = P.global_mean(V(b).with_cmul(0, C), name="gm")
-    outs = [V(o_add), V(o_pool), V(o_bil), V(o_ps), V(o_gate), V(o_gm)]
-    xs = [det_tensor("ew.x%d" % i, (N, C, H, W)) for i in range(3)]
-    xd = [x.double().requires_grad_(True) for x in xs]
-    sa, ha, sb, hb = [t.double().view(1, -1, 1, 1) for t in (aff_a[2], aff_a[3], aff_b[2], aff_b[3])]
+    affs = {}
+    for k in ("add.a", "bil", "gate.f", "gate.att"):
+        affs[k] = _affine_view(P, t[k], "ew." + k, C)
+    outs = [V(P.add_act(affs["add.a"][0], V(t["add.b"]), L.ACT_RELU, name="add")),
+            V(P.avgpool(V(t["pool"]).with_cmul(0, C), name="pool")),
+            V(P.bilinear(affs["bil"][0], name="bil")),
+            V(P.pixel_shuffle(V(t["ps"]).with_cmul(0, C), N * C, C // 4, name="ps")),
+            V(P.gate(affs["gate.f"][0], affs["gate.att"][0], t["gate.pcd"], name="gate")),
+            V(P.global_mean(V(t["gm"]).with_cmul(0, C), name="gm")),
+            V(P.maxpool(V(t["mp"]), name="mp"))]
+    xs = [det_tensor("ew.x." + k, (N, C, H, W)) for k in names]
+    xs[names.index("mp")] = xs[names.index("mp")] - 2.0          # all negative on a plain view: padding must act as -inf
+    xd = dict(zip(names, [x.double().requires_grad_(True) for x in xs]))
+    y = {}
+    for k, (_, (_, _, sc, sh)) in affs.items():
+        y[k] = xd[k] * sc.double().view(1, -1, 1, 1) + sh.double().view(1, -1, 1, 1)
+        y[k].retain_grad()
     cmd, cm2d = cm.double()[:, :, None, None], cm2.double()[:, :, None, None]
-    ya, yb = xd[0] * sa + ha, xd[1] * sb + hb
-    refs = [F.relu(ya + xd[2]), F.avg_pool2d(xd[0] * cmd, 3, 2, 1),
-            F.interpolate(yb, scale_factor=2, mode="bilinear", align_corners=False),
-            F.pixel_shuffle(xd[2] * cmd, 2) * cm2d, ya * torch.sigmoid(yb) + xd[2], (xd[1] * cmd).mean((2, 3), keepdim=True)]
+    refs = [F.relu(y["add.a"] + xd["add.b"]), F.avg_pool2d(xd["pool"] * cmd, 3, 2, 1),
+            F.interpolate(y["bil"], scale_factor=2, mode="bilinear", align_corners=False),
+            F.pixel_shuffle(xd["ps"] * cmd, 2) * cm2d, y["gate.f"] * torch.sigmoid(y["gate.att"]) + xd["gate.pcd"],
+            (xd["gm"] * cmd).mean((2, 3), keepdim=True), F.max_pool2d(xd["mp"], 3, 2, 1)]
+    assert refs[-1].max() < 0
     gouts = [det_tensor("ew.go%d" % i, r.shape) for i, r in enumerate(refs)]
     sum((r * g.double()).sum() for r, g in zip(refs, gouts)).backward()
     # finalise happens inside run(); affine constants are written right after (persist arena exists only then)
@@ -401,17 +411,14 @@ def test_elementwise_primitives_fwd_bwd():
 
     def fin():
         r = orig_finalise()
-        _set_affine(P, [aff_a, aff_b])
+        _set_affine(P, [a[1] for a in affs.values()])
         return r
     P.finalise = fin
     got, gin, _ = Hn.run(outs, xs, gouts)
-    for nm, g, r in zip(("add", "pool", "bil", "ps", "gate", "gm"), got, refs):
+    for nm, g, r in zip(("add", "pool", "bil", "ps", "gate", "gm", "mp"), got, refs):
         _check("ew." + nm, g, r.detach())
-    # gradients w.r.t. the raw inputs: views with a constant affine deliver dL/dy, so scale by d y/d x on the host
-    ga = gin[0]
-    # a: through va (scale sa) [add, gate] and directly [pool]  -> the plan accumulates dL/dy_a and dL/da in ONE buffer
-    # only when the view has no BN; here va is a distinct root, so compare the sum of both paths:
-    _check("ew.gin_c", gin[2], xd[2].grad, 1e-4)
+    for i, k in enumerate(names):
+        _check("ew.gin." + k, gin[i], (y[k] if k in y else xd[k]).grad, 1e-4)
 
 
 def test_maxpool_fwd_bwd():
