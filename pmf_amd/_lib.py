@@ -143,6 +143,21 @@ def lib():
     L.pmf_pack_tile_ci.argtypes = [C.c_int32, C.c_int32]
     L.pmf_pack_weights_batched.restype = C.c_int
     L.pmf_pack_weights_batched.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    L.pmf_bn_finalize.restype = C.c_int
+    L.pmf_bn_finalize.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+                                  C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    L.pmf_bn_eval_affine.restype = C.c_int
+    L.pmf_bn_eval_affine.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    L.pmf_bn_bwd_reduce.restype = C.c_int
+    L.pmf_bn_bwd_reduce.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pmf_bn_bwd_fold.restype = C.c_int
+    L.pmf_bn_bwd_fold.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pmf_bn_bwd_apply.restype = C.c_int
+    L.pmf_bn_bwd_apply.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                   C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
     L.pmf_bn_bwd_small_ok.restype = C.c_int
     L.pmf_bn_bwd_small_ok.argtypes = [C.c_int64, C.c_int32]
     L.pmf_bn_bwd_small.restype = C.c_int

@@ -48,6 +48,7 @@ __global__ void bn_finalize_k(const double* __restrict__ stats, int nrows, float
 extern "C" int pmf_bn_finalize(const double* stats, int32_t nrows, float count, const float* gamma, const float* beta,
                                float* running_mean, float* running_var, float momentum, float eps, float* scale,
                                float* shift, float* save_mean, float* save_invstd, int32_t C, pmf_stream_t s) {
+  if (nrows < 1 || C < 1 || !(count >= 1.f)) return PMF_E_ARG;
   hipLaunchKernelGGL(bn_finalize_k, dim3(C), dim3(256), 0, (hipStream_t)s, stats, nrows, count, gamma, beta,
                      running_mean, running_var, momentum, eps, scale, shift, save_mean, save_invstd, C);
   PMF_LAUNCH_CHECK();
@@ -68,6 +69,7 @@ __global__ void bn_eval_k(const float* __restrict__ gamma, const float* __restri
 extern "C" int pmf_bn_eval_affine(const float* gamma, const float* beta, const float* running_mean,
                                   const float* running_var, float eps, float* scale, float* shift, float* save_mean,
                                   float* save_invstd, int32_t C, pmf_stream_t s) {
+  if (C < 1) return PMF_E_ARG;
   hipLaunchKernelGGL(bn_eval_k, dim3(cdiv(C, 256)), dim3(256), 0, (hipStream_t)s, gamma, beta, running_mean, running_var,
                      eps, scale, shift, save_mean, save_invstd, C);
   PMF_LAUNCH_CHECK();
@@ -180,7 +182,7 @@ extern "C" int pmf_bn_bwd_reduce(const float* gy, int32_t gy_ldc, const float* a
                                  int32_t C, const float* save_mean, const float* gamma, const float* save_invstd,
                                  int32_t train, double* part, float* coef, float* dgamma, float* dbeta,
                                  pmf_stream_t s) {
-  if (C % 4) return PMF_E_ARG;
+  if (C % 4 || C < 4 || npix < 1) return PMF_E_ARG;
   ColL L = col_l(npix, C / 4);
   if (g_pmf_col_unroll == 8)
     hipLaunchKernelGGL(bn_bwd_reduce_k<8>, L.grid, L.block, 0, (hipStream_t)s, gy, gy_ldc, a, a_ldc, npix, C / 4, C,
@@ -197,7 +199,7 @@ extern "C" int pmf_bn_bwd_reduce(const float* gy, int32_t gy_ldc, const float* a
 extern "C" int pmf_bn_bwd_fold(const double* part, int32_t nrows, int32_t C, int64_t npix, int32_t train,
                                const float* gamma, const float* save_invstd, float* coef, float* dgamma, float* dbeta,
                                pmf_stream_t s) {
-  if (nrows < 1) return PMF_E_ARG;
+  if (nrows < 1 || C < 1 || npix < 1) return PMF_E_ARG;
   hipLaunchKernelGGL(bn_bwd_fold_k, dim3(C), dim3(256), 0, (hipStream_t)s, part, (int)nrows, C, 1.f / (float)npix, train,
                      gamma, save_invstd, coef, dgamma, dbeta);
   PMF_LAUNCH_CHECK();
@@ -255,7 +257,7 @@ __global__ void bn_bwd_apply_k(const float* __restrict__ gy, int gy_ldc, const f
 extern "C" int pmf_bn_bwd_apply(const float* gy, int32_t gy_ldc, const float* a, int32_t a_ldc, int64_t npix,
                                 int32_t C, const float* coef, const float* save_mean, int32_t act, float* dz,
                                 int32_t dz_ldc, float* dbias_rows, int32_t dbias_ld, pmf_stream_t s) {
-  if (C % 4) return PMF_E_ARG;
+  if (C % 4 || C < 4 || npix < 1) return PMF_E_ARG;
   ColL L = col_l(npix, C / 4);
   if (g_pmf_col_unroll == 8)
     hipLaunchKernelGGL(bn_bwd_apply_k<8>, L.grid, L.block, 0, (hipStream_t)s, gy, gy_ldc, a, a_ldc, npix, C / 4, C, coef,
