@@ -222,6 +222,13 @@ int pmf_conv_fwd_stat_rows(const pmf_conv_desc_t* d);
 int pmf_conv_fwd_stat_rows_max(const pmf_conv_desc_t* d);
 /* number of 16-channel K stages (after 64-channel stage merging) of this descriptor under cfg: bounds the K splits */
 int pmf_conv_fwd_kstages(const pmf_conv_desc_t* d);
+/* which kernel pmf_conv_fwd runs for this descriptor (nothing is launched): the PIPE number of the conv_fwd_k instantiation,
+ * PMF_CONV_WS_FAMILY for the wave-scheduled kernel (conv_ws_k), or the negative code pmf_conv_fwd would return.
+ * info = { BN, MT, K splits, combine (0 none / 1 in-kernel tickets / 2 second launch: conv_finish_k), partial-statistics rows
+ * (= pmf_conv_fwd_stat_rows), K stages (= pmf_conv_fwd_kstages), dynamic LDS bytes, grid x, y, z, and for the wave-scheduled
+ * kernel NCO and the A-slab variant (0 otherwise) } */
+int pmf_conv_fwd_variant(const pmf_conv_desc_t* d, int32_t info[12]);
+#define PMF_CONV_WS_FAMILY 100
 int pmf_bn_finalize(const double* stats, int32_t nrows, float count, const float* gamma, const float* beta,
                     float* running_mean, float* running_var, float momentum, float eps, float* scale, float* shift,
                     float* save_mean, float* save_invstd, int32_t C, pmf_stream_t s);

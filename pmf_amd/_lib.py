@@ -19,6 +19,7 @@ WG_UNIT, WG_PIPE, WG_STAGED, WG_SWP, WG_W8, WG_NSPLIT, WG_DIRECT, WG_DIRECT_S3, 
 PMF_E_ARG, PMF_E_UNSUPPORTED = -1, -2
 CFG_DIRECT_TAPS = 1 << 24      # pmf_conv_desc_t.cfg: direct multi-tap variant (PMF_CFG_DIRECT_TAPS)
 CFG_WS = 1 << 25               # ... the wave-scheduled N-split kernel (PMF_CFG_WS, csrc/conv_ws.hip)
+CONV_WS_FAMILY = 100           # pmf_conv_fwd_variant: conv_ws_k (PMF_CONV_WS_FAMILY); otherwise the PIPE of conv_fwd_k
 
 (OP_CONV, OP_WGRAD, OP_PACK, OP_BN_FINALIZE, OP_BN_EVAL, OP_BN_BWD_REDUCE, OP_BN_BWD_APPLY, OP_ADD_ACT,
  OP_ADD_ACT_BWD, OP_ACT_BWD, OP_AVGPOOL, OP_AVGPOOL_BWD, OP_MAXPOOL, OP_MAXPOOL_BWD, OP_BILINEAR,
@@ -137,6 +138,8 @@ def lib():
     L.pmf_conv_multi_ok.argtypes = [C.POINTER(ConvDesc)]
     L.pmf_conv_fwd_stat_rows.restype = C.c_int
     L.pmf_conv_fwd_stat_rows.argtypes = [C.POINTER(ConvDesc)]
+    L.pmf_conv_fwd_variant.restype = C.c_int
+    L.pmf_conv_fwd_variant.argtypes = [C.POINTER(ConvDesc), C.POINTER(C.c_int32 * 12)]
     L.pmf_col_rows.restype = C.c_int
     L.pmf_col_rows.argtypes = [C.c_int64, C.c_int32]
     L.pmf_pack_tile_ci.restype = C.c_int
@@ -331,7 +334,7 @@ def lib():
 
 EXPORTS = [
     "pmf_conv_fwd", "pmf_conv_wgrad", "pmf_conv_wgrad_partial", "pmf_conv_wgrad_reduce", "pmf_conv_wgrad_reduce_plan", "pmf_conv_wgrad_reduce_multi", "pmf_conv_wgrad_workspace", "pmf_conv_wgrad_nsplit", "pmf_conv_wgrad_variant", "pmf_pack_tile_ci",
-    "pmf_pack_weights_batched", "pmf_conv_fwd_stat_rows", "pmf_conv_s3_eligible", "pmf_conv_ws_ok", "pmf_conv_fwd_stat_rows_max", "pmf_conv_fwd_kstages", "pmf_col_rows", "pmf_bn_finalize", "pmf_bn_eval_affine", "pmf_bn_bwd_reduce", "pmf_bn_bwd_fold", "pmf_bn_bwd_apply",
+    "pmf_pack_weights_batched", "pmf_conv_fwd_stat_rows", "pmf_conv_s3_eligible", "pmf_conv_ws_ok", "pmf_conv_fwd_stat_rows_max", "pmf_conv_fwd_kstages", "pmf_conv_fwd_variant", "pmf_col_rows", "pmf_bn_finalize", "pmf_bn_eval_affine", "pmf_bn_bwd_reduce", "pmf_bn_bwd_fold", "pmf_bn_bwd_apply",
     "pmf_add_act", "pmf_add_act_bwd", "pmf_act_bwd", "pmf_avgpool3s2", "pmf_avgpool3s2_bwd", "pmf_maxpool3s2",
     "pmf_maxpool3s2_bwd", "pmf_bilinear2x", "pmf_bilinear2x_bwd", "pmf_pixel_shuffle2", "pmf_pixel_shuffle2_bwd",
     "pmf_fusion_gate", "pmf_fusion_gate_bwd", "pmf_global_mean", "pmf_global_mean_bwd", "pmf_broadcast_rows", "pmf_colsum", "pmf_colsum_rows",

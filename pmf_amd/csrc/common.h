@@ -105,3 +105,24 @@ struct ConvGeom {
   float* ws;        // [ksplit][N*OH*OW][ws_ld] partial sums (deterministic split-K)
   unsigned* tickets;  // non-NULL: the last workgroup to arrive at an output tile combines the slabs in-kernel (conv_epi.h)
 };
+
+// geometry of the wave-scheduled convolution (conv_ws.hip)
+struct WsGeom {
+  int segs_x_log2, th, tw, tiles_x, tiles_y;
+  int in_rows, in_cols, dy_min, dx_min;
+  int a_bytes;          // one input-tile buffer
+  int KS, CT;           // 16-channel chunks in all operands; 32-channel output tiles in the packed weights (ldw / 32)
+  int w_bytes;          // size of the packed weight array (buffer range)
+};
+
+// what conv_ws.hip tells the kernel selection of conv_fwd.hip (conv_pick) about a descriptor, in one pass
+struct WsPick {
+  int nco;              // output-channel tiles per workgroup (1 / 2 / 4); 0: not eligible
+  int asl;              // A-slab variant: 16-byte staging slots per thread (4 / 5)
+  int rows;             // partial-statistics rows of a launch (one per tile and sample); 0: the halo tile does not fit
+  int lds;              // dynamic LDS bytes
+  WsGeom g;
+  ConvGeom cg;
+};
+void conv_ws_pick(const pmf_conv_desc_t* d, WsPick* p);
+int conv_ws_run(const pmf_conv_desc_t* d, const WsPick& p, hipStream_t s);

@@ -1310,9 +1310,6 @@ static int finish_rows(const pmf_conv_desc_t* d, bool stats) {
 
 // the ticket array of the in-kernel combine holds one counter per output tile: PMF_SPLITK_TICKETS entries
 #define PMF_SPLITK_TICKETS 16384
-static bool conv_tickets_ok(const pmf_conv_desc_t* d, int tiles_mn) {
-  return d->splitk_tickets != nullptr && tiles_mn <= PMF_SPLITK_TICKETS;
-}
 
 // deterministic split-K tail of a launch whose workgroups wrote g.ksplit partial slabs
 static int pmf_conv_finish_launch(const pmf_conv_desc_t* d, const ConvGeom& g, hipStream_t s) {
@@ -1338,22 +1335,16 @@ extern "C" int pmf_conv_multi_ok(const pmf_conv_desc_t* d) {
   return d && d->ndst > 0 && d->ndst <= PMF_MAX_SRC && !d->bias && multi_tile(d) != 0;
 }
 
-static int conv_direct_lds(const pmf_conv_desc_t* d, int BN, int* kchunk = nullptr);
-static bool conv_stem_class(const pmf_conv_desc_t* d);
-static bool conv_s3_fits(const pmf_conv_desc_t* d, int MT);
-static bool conv_s3_stride2(const pmf_conv_desc_t* d);
-static void conv_config_(const pmf_conv_desc_t* d, int* BN, int* MT);
-static void conv_config(const pmf_conv_desc_t* d, int* BN, int* MT) {
-  conv_config_(d, BN, MT);
-  // 1x1 on split-bf16 weights: the direct variant was promised for the 32-wide tile (pmf_conv_s3_eligible); a 64-wide
-  // tile whose weight fragments do not fit LDS falls back to it
-  if (d->w_s3 && (d->ntaps == 1 || ((d->cfg >> 24) & 1) || conv_stem_class(d)) && *BN == 64 && !conv_direct_lds(d, 64) && conv_direct_lds(d, 32)) *BN = 32;
-  // LDS-staged split loop: the 256-pixel tile may not qualify where the 128-pixel one does (dilated 3x3 on a 4-row map)
-  if (d->w_s3 && d->ntaps > 1 && *MT == 2 && !conv_stem_class(d) && !((d->cfg >> 24) & 1) && !conv_s3_fits(d, 2)) *MT = 1;
-  if (d->w_s3 && d->in_stride == 2 && d->ntaps > 1) *MT = 1;      // the stride-2 split loop: 128-pixel tiles
-  if (d->ndst > 0 && *BN == 64 && multi_tile(d) == 32) *BN = 32;   // a 32-channel destination: no tile may straddle two
+// PMF_CONV_FORCE="BN,MT,KS" (tools/bench_conv.py sweeps; 0 = keep the heuristic), parsed once per call
+struct ConvForce { int bn, mt, ks; };
+static ConvForce conv_force() {
+  ConvForce f = {0, 0, 0};
+  if (const char* e = getenv("PMF_CONV_FORCE")) sscanf(e, "%d,%d,%d", &f.bn, &f.mt, &f.ks);
+  return f;
 }
-static void conv_config_(const pmf_conv_desc_t* d, int* BN, int* MT) {
+
+// tile before the per-family corrections of conv_pick: caller-tuned (cfg), else by the size of the grid
+static void conv_tile(const pmf_conv_desc_t* d, const ConvForce& f, int* BN, int* MT) {
   if (d->cfg) {                       // caller-tuned tile configuration
     const int bn = d->cfg & 0xff, mt = (d->cfg >> 8) & 0xff;
     *BN = (bn == 64 && d->Cout > 32) ? 64 : 32;
@@ -1368,44 +1359,49 @@ static void conv_config_(const pmf_conv_desc_t* d, int* BN, int* MT) {
   // double the grid (measured +5 % on 128 -> 128 at 16x512); below 200 the K loop is split instead
   const long b64 = (long)d->N * cdiv(d->OH, 4) * cdiv(d->OW, 32) * cdiv(d->Cout, 64);
   if (*MT == 1 && *BN == 64 && b64 >= 200 && b64 < 512) *BN = 32;
-  if (const char* e = getenv("PMF_CONV_FORCE")) {   // tools/bench_conv.py sweeps: "BN,MT,KS" (0 = keep the heuristic)
-    int bn = 0, mt = 0, ks = 0;
-    sscanf(e, "%d,%d,%d", &bn, &mt, &ks);
-    if (bn == 32 || (bn == 64 && d->Cout > 32)) *BN = bn;
-    if (mt == 1 || mt == 2) *MT = mt;
-  }
+  if (f.bn == 32 || (f.bn == 64 && d->Cout > 32)) *BN = f.bn;
+  if (f.mt == 1 || f.mt == 2) *MT = f.mt;
 }
 
 // split-K factor: only when the M x N grid cannot fill the 256 CUs (low-resolution, many-channel layers)
-static int choose_ksplit(const pmf_conv_desc_t* d, int blocks_mn, int nchunks, int mfma_per_chunk) {
-  if (const char* e = getenv("PMF_CONV_FORCE")) {   // sweeps only
-    int bn = 0, mt = 0, ks = 0;
-    sscanf(e, "%d,%d,%d", &bn, &mt, &ks);
-    if (ks >= 1 && d->splitk_ws) {
-      int k = ks > nchunks ? nchunks : ks;
-      if (k > 32) k = 32;
-      const int64_t sl = (int64_t)d->N * d->OH * d->OW * round_up(d->Cout, 4) * 4;
-      while (k > 1 && sl * k > d->splitk_ws_bytes) --k;
-      return k < 2 ? 1 : k;
-    }
-  }
-  if (d->cfg && ((d->cfg >> 16) & 0xff)) {     // caller-tuned number of K splits
-    int k = (d->cfg >> 16) & 0xff;
+static int choose_ksplit(const pmf_conv_desc_t* d, int blocks_mn, int nchunks, int forced) {
+  int k;
+  if (forced >= 1 && d->splitk_ws) {                  // PMF_CONV_FORCE: sweeps only
+    k = forced;
+  } else if (d->cfg && ((d->cfg >> 16) & 0xff)) {     // caller-tuned number of K splits
     if (!d->splitk_ws || blocks_mn > 1024) return 1;
-    if (k > nchunks) k = nchunks;
-    if (k > 32) k = 32;
-    const int64_t sl = (int64_t)d->N * d->OH * d->OW * round_up(d->Cout, 4) * 4;
-    while (k > 1 && sl * k > d->splitk_ws_bytes) --k;
-    return k < 2 ? 1 : k;
+    k = (d->cfg >> 16) & 0xff;
+  } else {
+    if (!d->splitk_ws || blocks_mn >= 200 || nchunks < 4) return 1;
+    k = 512 / (blocks_mn > 0 ? blocks_mn : 1);
+    // (a floor on the MFMA work per split was tried: the serial K loop of 1x1 layers is slower)
+    if (k > nchunks / 2) k = nchunks / 2;
   }
-  if (!d->splitk_ws || blocks_mn >= 200 || nchunks < 4) return 1;
-  int k = 512 / (blocks_mn > 0 ? blocks_mn : 1);
-  if (k > nchunks / 2) k = nchunks / 2;
-  (void)mfma_per_chunk;   // (a floor on the MFMA work per split was tried: the serial K loop of 1x1 layers is slower)
+  if (k > nchunks) k = nchunks;
   if (k > 32) k = 32;
-  const int64_t slab = (int64_t)d->N * d->OH * d->OW * round_up(d->Cout, 4) * 4;
+  const int64_t slab = (int64_t)d->N * d->OH * d->OW * round_up(d->Cout, 4) * 4;      // the workspace holds k partial slabs
   while (k > 1 && slab * k > d->splitk_ws_bytes) --k;
   return k < 2 ? 1 : k;
+}
+
+// operands of the pipelined / direct / split loops: multiples of 16 channels with the same H x W, no broadcast, 32-bit offsets
+static bool conv_srcs_uniform(const pmf_conv_desc_t* d) {
+  for (int i = 0; i < d->nsrc; ++i) {
+    if (d->src[i].C % 16 || (d->src[i].flags & PMF_SRC_BCAST)) return false;
+    if (d->src[i].H != d->src[0].H || d->src[i].W != d->src[0].W) return false;
+    if ((int64_t)d->N * d->src[i].H * d->src[i].W * d->src[i].ldc * 4 >= (1ll << 31)) return false;
+  }
+  return true;
+}
+static int conv_kc_alloc(const pmf_conv_desc_t* d) {     // rows per tap of the LDS weight tile: the widest operand, <= KC
+  int cmax = 0;
+  for (int i = 0; i < d->nsrc; ++i) cmax = d->src[i].C > cmax ? d->src[i].C : cmax;
+  return cmax < KC ? cmax : KC;
+}
+static int conv_stages(const pmf_conv_desc_t* d, int kc) {     // K stages of kc channels (every operand a multiple of kc)
+  int n = 0;
+  for (int i = 0; i < d->nsrc; ++i) n += d->src[i].C / kc;
+  return n;
 }
 
 // K-loop variant: 0 generic, 1 software-pipelined (halo tile, 1/3/4/9 taps, stride 1, operands multiples of 16
@@ -1413,13 +1409,9 @@ static int choose_ksplit(const pmf_conv_desc_t* d, int blocks_mn, int nchunks, i
 static int conv_pipe_mode(const pmf_conv_desc_t* d, const ConvGeom& g, int gather, int MT) {
   if (gather || d->in_stride != 1) return 0;
   if (d->ntaps != 1 && d->ntaps != 2 && d->ntaps != 3 && d->ntaps != 4 && d->ntaps != 9) return 0;
+  if (!conv_srcs_uniform(d)) return 0;
   bool c64 = true;
-  for (int i = 0; i < d->nsrc; ++i) {
-    if (d->src[i].C % 16 || (d->src[i].flags & PMF_SRC_BCAST)) return 0;
-    if (d->src[i].H != d->src[0].H || d->src[i].W != d->src[0].W) return 0;
-    if ((int64_t)d->N * d->src[i].H * d->src[i].W * d->src[i].ldc * 4 >= (1ll << 31)) return 0;
-    c64 = c64 && d->src[i].C % 64 == 0;
-  }
+  for (int i = 0; i < d->nsrc; ++i) c64 = c64 && d->src[i].C % 64 == 0;
   if (g.in_rows * g.in_cols * 4 > 256 * (MT == 2 ? 7 : 5)) return 0;
   if (d->ntaps == 1 && MT == 1 && c64 && g.in_rows * g.in_cols == 128) return 4;
   return 1;
@@ -1439,27 +1431,22 @@ static bool conv_stem_class(const pmf_conv_desc_t* d) {
   return on && d->nsrc == 1 && d->src[0].C == 8 && d->ntaps >= 2 && d->ntaps <= PMF_MAX_TAPS &&
          !(d->src[0].flags & PMF_SRC_BCAST);
 }
-static int conv_direct_lds(const pmf_conv_desc_t* d, int BN, int* kchunk) {
-  constexpr bool off = false;
+static int conv_direct_lds(const pmf_conv_desc_t* d, int BN, int* kchunk = nullptr) {
   constexpr int stream_kib = 96;
   if (kchunk) *kchunk = 0;
   // more than one tap: only on request (cfg bit 24, set by the plan autotuner when the variant measured faster), <= 9 taps
   const bool mtap = d->ntaps > 1;
   const bool stem = conv_stem_class(d);       // 8 padded channels, many taps: two taps per MFMA step (PIPE 14)
   if (mtap && !stem && (!((d->cfg >> 24) & 1) || d->ntaps > TAPG)) return 0;
-  if (off || !d->w_s3 || (d->gather && !stem) || (d->ldw & 31)) return 0;
+  if (!d->w_s3 || (d->gather && !stem) || (d->ldw & 31)) return 0;
   if (stem) {
     if ((int64_t)d->N * d->src[0].H * d->src[0].W * d->src[0].ldc * 4 >= (1ll << 31)) return 0;
     const int lds_ = ((d->ntaps + 1) / 2) * (BN / 32) * 3 * 1024 + 16 * 8 + 256;
     return lds_ > 160 * 1024 ? 0 : (lds_ < 2 * 4 * 64 * 2 * 8 ? 2 * 4 * 64 * 2 * 8 : lds_);
   }
+  if (!conv_srcs_uniform(d)) return 0;
   int Ktot = 0;
-  for (int i = 0; i < d->nsrc; ++i) {
-    if (d->src[i].C % 16 || (d->src[i].flags & PMF_SRC_BCAST)) return 0;
-    if (d->src[i].H != d->src[0].H || d->src[i].W != d->src[0].W) return 0;
-    if ((int64_t)d->N * d->src[i].H * d->src[i].W * d->src[i].ldc * 4 >= (1ll << 31)) return 0;
-    Ktot += d->src[i].C;
-  }
+  for (int i = 0; i < d->nsrc; ++i) Ktot += d->src[i].C;
   const int NT = BN / 32, tab = 16 * Ktot + 256, steps = (Ktot / 16) * d->ntaps;
   int lds = steps * NT * 3 * 1024 + tab;
   if (lds < 2 * 4 * 64 * 2 * 8) lds = 2 * 4 * 64 * 2 * 8;
@@ -1479,260 +1466,244 @@ static int conv_direct_lds(const pmf_conv_desc_t* d, int BN, int* kchunk) {
 
 // split-bf16 path: 16-channel slabs per stage (1, 2 or 4) -- see conv_kloop_s3
 static int conv_s3_slabs(const pmf_conv_desc_t* d, const ConvGeom& g) {
-  int cap = 4;
   for (int c = 4; c >= 2; c >>= 1) {
-    if (c > cap || d->ntaps * c > TAPG || g.in_rows * g.in_cols * 4 * c > 256 * 8) continue;
+    if (d->ntaps * c > TAPG || g.in_rows * g.in_cols * 4 * c > 256 * 8) continue;
     bool ok = true;
     for (int i = 0; i < d->nsrc; ++i) ok = ok && d->src[i].C % (KC * c) == 0;
     if (ok) return c;
   }
   return 1;
 }
-
-template <int BN, int MT>
-static int launch(const pmf_conv_desc_t* d, hipStream_t s) {
-  ConvGeom g;
-  int Ktot = 0, cmax = 0, nchunks = 0;
-  for (int i = 0; i < d->nsrc; ++i) {
-    Ktot += d->src[i].C; cmax = d->src[i].C > cmax ? d->src[i].C : cmax; nchunks += cdiv(d->src[i].C, KC);
-  }
-  int gather;
-  int lds = pmf_conv_geometry(d->OH, d->OW, d->ntaps, d->tdy, d->tdx, d->in_stride, d->gather, BN, MT,
-                              cmax < KC ? cmax : KC, &g, &gather);
-  if (lds > 160 * 1024) return PMF_E_UNSUPPORTED;
-  // 32-bit byte offsets in the epilogue (buffer stores): every tensor it touches must stay below 2 GiB
-  if ((int64_t)d->N * d->out_H * d->out_W * d->out_ldc * 4 >= (1ll << 31)) return PMF_E_UNSUPPORTED;
-  if (d->ep_relu_x && (int64_t)d->N * d->out_H * d->out_W * d->ep_relu_ldc * 4 >= (1ll << 31)) return PMF_E_UNSUPPORTED;
-  if (d->ep_stat_mean && (!d->stats || !d->ep_relu_x)) return PMF_E_ARG;
-  if ((d->ep_flags & PMF_EP_STAT_X_ONLY) && !d->ep_stat_mean) return PMF_E_ARG;
-  g.Ktot = Ktot;
-  pmf_conv_desc_t dd = *d;
-  dd.gather = gather;
-  // the 160 KiB dynamic-LDS attribute is per device: set it again when the current device changes (one bit per device)
-  static unsigned long long attr_devs = 0ull;
-  if (pmf_first_on_device(&attr_devs)) {
-    (void)hipFuncSetAttribute((const void*)conv_fwd_k<BN, MT, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_fwd_k<BN, MT, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if constexpr (MT == 1)
-      (void)hipFuncSetAttribute((const void*)conv_fwd_k<BN, 1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_fwd_k<BN, MT, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_fwd_k<BN, MT, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_fwd_k<BN, MT, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_fwd_k<BN, MT, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_fwd_k<BN, MT, 10>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_fwd_k<BN, MT, 11>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_fwd_k<BN, MT, 13>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_fwd_k<BN, MT, 14>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if constexpr (MT == 1)
-      (void)hipFuncSetAttribute((const void*)conv_fwd_k<BN, 1, 12>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
-  const int co_tiles = cdiv(d->Cout, BN);
-  int mode = conv_pipe_mode(d, g, gather, MT);
-  g.kchunk = 0;
-  if (const int dl = conv_direct_lds(d, BN, &g.kchunk)) {   // 1x1 on split-bf16 weights: no input tile in LDS, no K split
-    mode = conv_stem_class(d) ? 14 : (d->ntaps > 1 ? 13 : 11);
-    lds = dl;
-    nchunks = 1;
-  } else if (d->w_s3 && d->in_stride == 2) {     // stride-2 3x3
-    if constexpr (MT != 1) return PMF_E_UNSUPPORTED;
-    if (!conv_s3_stride2(d) || (d->ldw & 31)) return PMF_E_UNSUPPORTED;
-    mode = 12;
-    g.a_floats = round_up(g.in_rows * g.in_cols * (S3_APB / 4), 4);
-    lds = g.a_floats * 4 + 9 * (BN / 32) * 3 * 1024 + 2048;
-    nchunks = 0;
-    for (int i = 0; i < d->nsrc; ++i) nchunks += d->src[i].C / KC;
-    if (lds > 160 * 1024) return PMF_E_UNSUPPORTED;
-  } else if (d->w_s3) {      // split-bf16 weights: the pipelined class only (pmf_conv_s3_eligible)
-    if (mode == 0 || (d->ldw & 31)) return PMF_E_UNSUPPORTED;
-    const int sl = conv_s3_slabs(d, g);
-    mode = sl == 4 ? 7 : (sl == 2 ? 6 : 5);
-    g.a_floats = sl * round_up(g.in_rows * g.in_cols * (S3_APB / 4), 4);
-    lds = g.a_floats * 4 + d->ntaps * sl * (BN / 32) * 3 * 1024 + 2048;   // + per-thread scratch of the staging stores
-    if (sl == 1 && d->ntaps == 9) mode = 8;
-    if (sl == 2 && d->ntaps == 4) mode = 10;
-    nchunks = 0;
-    for (int i = 0; i < d->nsrc; ++i) nchunks += d->src[i].C / (KC * sl);
-    if (lds < 2 * 4 * 64 * 2 * 8) lds = 2 * 4 * 64 * 2 * 8;
-    if (lds > 160 * 1024) return PMF_E_UNSUPPORTED;
-  } else if (!d->w) {
-    return PMF_E_ARG;
-  }
-  if (mode == 4) {           // 64-channel stages
-    nchunks = 0;
-    for (int i = 0; i < d->nsrc; ++i) nchunks += d->src[i].C / (KC * 4);
-    lds = (g.a_floats * 4 + 4 * KC * BN) * 4;
-  }
-  if (d->ndst > 0 && !pmf_conv_multi_ok(d)) return PMF_E_ARG;
-  g.ksplit = d->ndst > 0 ? 1 : choose_ksplit(d, g.tiles_x * g.tiles_y * d->N * co_tiles, nchunks, d->ntaps * 8 * MT * (BN / 32));
-  g.ws = d->splitk_ws;
-  g.ws_ld = round_up(d->Cout, 4);
-  // in-kernel combine by the last-arriving workgroup of an output tile (conv_epi.h) when the caller gave a ticket array
-  g.tickets = (g.ksplit > 1 && conv_tickets_ok(d, g.tiles_x * g.tiles_y * d->N * co_tiles)) ? d->splitk_tickets : nullptr;
-  g.one = (d->nsrc == 1 && g.ksplit == 1) ? 1 : 0;
-  dim3 grid(g.tiles_x * g.tiles_y, co_tiles * g.ksplit, d->N);
-  if (mode == 12) {
-    if constexpr (MT == 1) hipLaunchKernelGGL((conv_fwd_k<BN, 1, 12>), grid, dim3(256), lds, s, dd, g);
-  } else if (mode == 11) {
-    hipLaunchKernelGGL((conv_fwd_k<BN, MT, 11>), grid, dim3(256), lds, s, dd, g);
-  } else if (mode == 13) {
-    hipLaunchKernelGGL((conv_fwd_k<BN, MT, 13>), grid, dim3(256), lds, s, dd, g);
-  } else if (mode == 14) {
-    hipLaunchKernelGGL((conv_fwd_k<BN, MT, 14>), grid, dim3(256), lds, s, dd, g);
-  } else if (mode == 5) {
-    hipLaunchKernelGGL((conv_fwd_k<BN, MT, 5>), grid, dim3(256), lds, s, dd, g);
-  } else if (mode == 6) {
-    hipLaunchKernelGGL((conv_fwd_k<BN, MT, 6>), grid, dim3(256), lds, s, dd, g);
-  } else if (mode == 7) {
-    hipLaunchKernelGGL((conv_fwd_k<BN, MT, 7>), grid, dim3(256), lds, s, dd, g);
-  } else if (mode == 8) {
-    hipLaunchKernelGGL((conv_fwd_k<BN, MT, 8>), grid, dim3(256), lds, s, dd, g);
-  } else if (mode == 10) {
-    hipLaunchKernelGGL((conv_fwd_k<BN, MT, 10>), grid, dim3(256), lds, s, dd, g);
-  } else if (mode == 4) {
-    if constexpr (MT == 1) hipLaunchKernelGGL((conv_fwd_k<BN, 1, 4>), grid, dim3(256), lds, s, dd, g);
-  } else if (mode == 1) {
-    g.kc_alloc = KC;   // the pipelined loop lays the weight slab out as [tap][16][BN]
-    hipLaunchKernelGGL((conv_fwd_k<BN, MT, 1>), grid, dim3(256), lds, s, dd, g);
-  } else {
-    hipLaunchKernelGGL((conv_fwd_k<BN, MT, 0>), grid, dim3(256), lds, s, dd, g);
-  }
-  PMF_LAUNCH_CHECK();
-  if (g.ksplit > 1 && !g.tickets) return pmf_conv_finish_launch(&dd, g, s);
-  return 0;
+// LDS bytes of the LDS-staged split loops (PIPE 5-10, 12): sl input slabs, the weight fragments of ntaps x sl stages for BN
+// output channels, the per-thread scratch of the staging stores
+static int conv_s3_lds(const ConvGeom& g, int ntaps, int sl, int BN) {
+  return sl * round_up(g.in_rows * g.in_cols * (S3_APB / 4), 4) * 4 + ntaps * sl * (BN / 32) * 3 * 1024 + 2048;
 }
-
-// the wave-scheduled N-split kernel (conv_ws.hip): on request -- cfg bit 25 (PMF_CFG_WS, set by the plan autotuner where it
-// measured faster) or PMF_CONV_WS=1 (every eligible launch with at least 128 workgroups: A/B) -- and eligible
-extern "C" int pmf_conv_ws_ok(const pmf_conv_desc_t* d);
-extern "C" int pmf_conv_ws_rows(const pmf_conv_desc_t* d);
-extern "C" int pmf_conv_ws_launch(const pmf_conv_desc_t* d, pmf_stream_t st);
-static bool conv_ws_wanted(const pmf_conv_desc_t* d) {
-  static const int force = getenv("PMF_CONV_WS") ? atoi(getenv("PMF_CONV_WS")) : -1;     // 0: never, 1: wherever eligible
-  constexpr int min_wgs = 128;
-  if (force == 0) return false;
-  const bool asked = (d->cfg >> 25) & 1;
-  if (!asked && force != 1) return false;
-  const int nco = pmf_conv_ws_ok(d);
-  if (!nco) return false;
-  if (asked) return true;
-  return pmf_conv_ws_rows(d) * (d->Cout / (32 * nco)) >= min_wgs;
-}
-
-// number of partial-statistics rows pmf_conv_fwd writes for this descriptor (stats must hold rows*2*Cout doubles)
-extern "C" int pmf_conv_fwd_stat_rows(const pmf_conv_desc_t* d) {
-  if (conv_ws_wanted(d)) return pmf_conv_ws_rows(d);
-  int BN, MT, gather, Ktot = 0, cmax = 0, nchunks = 0;
-  conv_config(d, &BN, &MT);
-  for (int i = 0; i < d->nsrc; ++i) {
-    Ktot += d->src[i].C; cmax = d->src[i].C > cmax ? d->src[i].C : cmax; nchunks += cdiv(d->src[i].C, KC);
-  }
-  ConvGeom g;
-  pmf_conv_geometry(d->OH, d->OW, d->ntaps, d->tdy, d->tdx, d->in_stride, d->gather, BN, MT, cmax < KC ? cmax : KC, &g,
-                    &gather);
-  const int tiles = g.tiles_x * g.tiles_y;
-  if (!d->w_s3 && conv_pipe_mode(d, g, gather, MT) == 4) {      // same stage count as launch<>()
-    nchunks = 0;
-    for (int i = 0; i < d->nsrc; ++i) nchunks += d->src[i].C / (KC * 4);
-  }
-  if (d->w_s3 && conv_pipe_mode(d, g, gather, MT) != 0) {
-    const int sl = conv_s3_slabs(d, g);
-    nchunks = 0;
-    for (int i = 0; i < d->nsrc; ++i) nchunks += d->src[i].C / (KC * sl);
-  }
-  if (conv_direct_lds(d, BN)) nchunks = 1;
-  if (d->ndst > 0) return tiles * d->N;
-  if (choose_ksplit(d, tiles * d->N * cdiv(d->Cout, BN), nchunks, d->ntaps * 8 * MT * (BN / 32)) > 1 &&
-      !conv_tickets_ok(d, tiles * d->N * cdiv(d->Cout, BN))) return finish_rows(d, true);
-  return tiles * d->N;
-}
-
-extern "C" int pmf_conv_s3_eligible(const pmf_conv_desc_t* d) {
-  if (conv_stem_class(d)) {   // 3: weights in pack format 2
-    pmf_conv_desc_t t = *d;
-    t.w_s3 = (const void*)1;
-    if (!t.ldw) t.ldw = 64;
-    return conv_direct_lds(&t, 32) ? 3 : 0;
-  }
-  if (d->ntaps == 1) {       // 1x1: only the direct variant (2), judged on the narrow tile; the caller sets w_s3 afterwards
-    pmf_conv_desc_t t = *d;
-    t.w_s3 = (const void*)1;
-    if (!t.ldw) t.ldw = 64;
-    return conv_direct_lds(&t, 32) ? 2 : 0;
-  }
-  return conv_s3_fits(d, 1) ? 1 : 0;      // (a 256-pixel tile that does not qualify falls back to 128 pixels: conv_config)
-}
+// ... as the eligibility rules judge it before the tile is known: on the 64-wide tile, 16 bytes per slab in hand
+static bool conv_s3_lds_fits(const ConvGeom& g, int ntaps, int sl) { return conv_s3_lds(g, ntaps, sl, 64) + 16 * sl <= 160 * 1024; }
 
 // stride-2 3x3 layers on the split loop (PIPE 12): all nine taps live, halo tile of the 4 x 32-pixel output tile
 // (9 x 65 input pixels) within ten staging slots per thread and the LDS budget of the 64-wide tile
 static bool conv_s3_stride2(const pmf_conv_desc_t* d) {
-  if (d->in_stride != 2 || d->ntaps != 9 || d->gather) return false;
-  for (int i = 0; i < d->nsrc; ++i) {
-    if (d->src[i].C % 16 || (d->src[i].flags & PMF_SRC_BCAST)) return false;
-    if (d->src[i].H != d->src[0].H || d->src[i].W != d->src[0].W) return false;
-    if ((int64_t)d->N * d->src[i].H * d->src[i].W * d->src[i].ldc * 4 >= (1ll << 31)) return false;
-  }
-  int cmax = 0;
-  for (int i = 0; i < d->nsrc; ++i) cmax = d->src[i].C > cmax ? d->src[i].C : cmax;
+  if (d->in_stride != 2 || d->ntaps != 9 || d->gather || !conv_srcs_uniform(d)) return false;
   ConvGeom g;
   int gather;
-  pmf_conv_geometry(d->OH, d->OW, d->ntaps, d->tdy, d->tdx, 2, 0, 64, 1, cmax < KC ? cmax : KC, &g, &gather);
+  // the 64 x 128-pixel tile, whatever the launch chose: the class is promised to the plan before cfg is known, PIPE 12 runs
+  // 128-pixel tiles only and the 64-wide tile needs the most LDS
+  pmf_conv_geometry(d->OH, d->OW, d->ntaps, d->tdy, d->tdx, 2, 0, 64, 1, conv_kc_alloc(d), &g, &gather);
   if (gather || g.in_rows * g.in_cols * 4 > 256 * 10) return false;
-  return g.in_rows * g.in_cols * S3_APB + 16 + 9 * 2 * 3 * 1024 + 2048 <= 160 * 1024;
+  return conv_s3_lds_fits(g, 9, 1);
 }
 
 // the LDS-staged split loop with MT x 128-pixel tiles: pipelined class + LDS budget (judged on the 64-wide tile)
 static bool conv_s3_fits(const pmf_conv_desc_t* d, int MT) {
   if (d->in_stride == 2) return MT == 1 && conv_s3_stride2(d);
-  int cmax = 0;
-  for (int i = 0; i < d->nsrc; ++i) cmax = d->src[i].C > cmax ? d->src[i].C : cmax;
   ConvGeom g;
   int gather;
-  pmf_conv_geometry(d->OH, d->OW, d->ntaps, d->tdy, d->tdx, d->in_stride, d->gather, 64, MT, cmax < KC ? cmax : KC, &g,
-                    &gather);
+  // the 64-wide tile of MT x 128 pixels the caller asks about (pmf_conv_s3_eligible: 128 pixels, before cfg is known;
+  // conv_pick: 256 pixels, to fall back to 128 where they do not qualify), not the chosen one
+  pmf_conv_geometry(d->OH, d->OW, d->ntaps, d->tdy, d->tdx, d->in_stride, d->gather, 64, MT, conv_kc_alloc(d), &g, &gather);
   if (conv_pipe_mode(d, g, gather, MT) == 0) return false;
-  const int sl = conv_s3_slabs(d, g);
-  return sl * (g.in_rows * g.in_cols * S3_APB + 16) + d->ntaps * sl * 2 * 3 * 1024 + 2048 <= 160 * 1024;
+  return conv_s3_lds_fits(g, d->ntaps, conv_s3_slabs(d, g));
+}
+
+extern "C" int pmf_conv_s3_eligible(const pmf_conv_desc_t* d) {
+  if (conv_stem_class(d) || d->ntaps == 1) {
+    // stem class (3: weights in pack format 2) and 1x1 (2: only the direct variant), judged on the narrow tile; the caller sets
+    // w_s3 afterwards
+    pmf_conv_desc_t t = *d;
+    t.w_s3 = (const void*)1;
+    if (!t.ldw) t.ldw = 64;
+    return conv_direct_lds(&t, 32) ? (conv_stem_class(d) ? 3 : 2) : 0;
+  }
+  return conv_s3_fits(d, 1) ? 1 : 0;      // (a 256-pixel tile that does not qualify falls back to 128 pixels: conv_pick)
 }
 
 extern "C" int pmf_conv_fwd_stat_rows_max(const pmf_conv_desc_t* d) {
-  int gather, cmax = 0;
-  for (int i = 0; i < d->nsrc; ++i) cmax = d->src[i].C > cmax ? d->src[i].C : cmax;
   ConvGeom g;
-  pmf_conv_geometry(d->OH, d->OW, d->ntaps, d->tdy, d->tdx, d->in_stride, d->gather, 32, 1, cmax < KC ? cmax : KC, &g,
-                    &gather);
-  const int rows = g.tiles_x * g.tiles_y * d->N;     // 128-pixel tiles give the most rows; split-K gives <= 1024
+  int gather;
+  // the 32 x 128-pixel tile: 128-pixel tiles give the most rows of every tile cfg may select; split-K gives <= 1024
+  pmf_conv_geometry(d->OH, d->OW, d->ntaps, d->tdy, d->tdx, d->in_stride, d->gather, 32, 1, conv_kc_alloc(d), &g, &gather);
+  const int rows = g.tiles_x * g.tiles_y * d->N;
   return rows > 1024 ? rows : 1024;
 }
 
-extern "C" int pmf_conv_fwd_kstages(const pmf_conv_desc_t* d) {
-  int BN, MT, gather, cmax = 0, nchunks = 0;
-  conv_config(d, &BN, &MT);
-  for (int i = 0; i < d->nsrc; ++i) { cmax = d->src[i].C > cmax ? d->src[i].C : cmax; nchunks += cdiv(d->src[i].C, KC); }
-  ConvGeom g;
-  pmf_conv_geometry(d->OH, d->OW, d->ntaps, d->tdy, d->tdx, d->in_stride, d->gather, BN, MT, cmax < KC ? cmax : KC, &g,
-                    &gather);
-  if (!d->w_s3 && conv_pipe_mode(d, g, gather, MT) == 4) {
-    nchunks = 0;
-    for (int i = 0; i < d->nsrc; ++i) nchunks += d->src[i].C / (KC * 4);
-  }
-  if (d->w_s3 && conv_pipe_mode(d, g, gather, MT) != 0) {
-    const int sl = conv_s3_slabs(d, g);
-    nchunks = 0;
-    for (int i = 0; i < d->nsrc; ++i) nchunks += d->src[i].C / (KC * sl);
-  }
-  if (conv_direct_lds(d, BN)) nchunks = 1;
-  return nchunks;
+// ---------------------------------------------------------------------------------------------------------------------------
+// The kernel selection.  conv_pick() answers once, for a descriptor, which kernel runs, on which tile, with how many K stages
+// and K splits, combined where, on which grid, with how much LDS and how many partial-statistics rows; the launch,
+// pmf_conv_fwd_stat_rows, pmf_conv_fwd_kstages and pmf_conv_fwd_variant all read the same ConvPick.  (The plan sizes the float64
+// partial-row buffer from the row count and the BatchNorm finalize reads exactly that many rows: a count computed for another
+// kernel than the one launched is an out-of-bounds write, or uninitialised rows in the batch statistics.)
+enum { CONV_WS = PMF_CONV_WS_FAMILY };                        // family: the PIPE of conv_fwd_k, or the wave-scheduled kernel
+enum { COMBINE_NONE = 0, COMBINE_TICKETS = 1, COMBINE_FINISH = 2 };     // K splits: in-kernel tickets / conv_finish_k
+struct ConvPick {
+  int rc;               // 0, or what pmf_conv_fwd returns instead of launching
+  int family, BN, MT;
+  ConvGeom g;           // as the chosen family needs it
+  int gather;           // effective gather mode (the halo tile of a gather == 0 request may not fit LDS)
+  int nchunks;          // K stages (wave-scheduled: of the conv_fwd_k selection it replaces, which the tuner sizes K splits from)
+  int combine, stat_rows, lds;
+  dim3 grid;
+  WsPick ws;            // wave-scheduled: NCO, A-slab variant, WsGeom
+};
+
+// the wave-scheduled N-split kernel (conv_ws.hip): on request -- cfg bit 25 (PMF_CFG_WS, set by the plan autotuner where it
+// measured faster) or PMF_CONV_WS=1 (every eligible launch with at least 128 workgroups: A/B) -- and eligible
+static bool conv_ws_wanted(const pmf_conv_desc_t* d, WsPick* w) {
+  static const int force = getenv("PMF_CONV_WS") ? atoi(getenv("PMF_CONV_WS")) : -1;     // 0: never, 1: wherever eligible
+  constexpr int min_wgs = 128;
+  const bool asked = (d->cfg >> 25) & 1;
+  w->nco = w->rows = 0;
+  if (force == 0 || (!asked && force != 1)) return false;
+  conv_ws_pick(d, w);
+  return w->nco && (asked || w->rows * (d->Cout / (32 * w->nco)) >= min_wgs);
 }
 
-extern "C" int pmf_conv_fwd(const pmf_conv_desc_t* d, pmf_stream_t st) {
-  hipStream_t s = (hipStream_t)st;
+static void conv_pick(const pmf_conv_desc_t* d, ConvPick* p) {
+  const ConvForce force = conv_force();
+  ConvGeom& g = p->g;
+  p->rc = 0;
+  auto refuse = [p](int rc) { if (!p->rc) p->rc = rc; };     // (the first refusal is the return code; the rest is still filled in)
+  int BN, MT;
+  conv_tile(d, force, &BN, &MT);
+  if (d->ndst > 0 && BN == 64 && multi_tile(d) == 32) BN = 32;    // a 32-channel destination: no tile may straddle two
+  // 1x1 / stem class / multi-tap on request (cfg bit 24) on split-bf16 weights: the direct variant -- no input tile in LDS, no K
+  // split.  It was promised for the 32-wide tile (pmf_conv_s3_eligible); a 64-wide tile whose weight fragments do not fit LDS
+  // falls back to it
+  g.kchunk = 0;
+  int direct = conv_direct_lds(d, BN, &g.kchunk);
+  if (!direct && BN == 64 && (direct = conv_direct_lds(d, 32, &g.kchunk)) != 0) BN = 32;
+  // LDS-staged split loop: the stride-2 form has 128-pixel tiles only, and the 256-pixel tile may not qualify where the
+  // 128-pixel one does (dilated 3x3 on a 4-row map)
+  if (d->w_s3 && d->ntaps > 1 && MT == 2 &&
+      (d->in_stride == 2 || (!conv_stem_class(d) && !((d->cfg >> 24) & 1) && !conv_s3_fits(d, 2)))) MT = 1;
+  p->BN = BN; p->MT = MT;
+  int lds = pmf_conv_geometry(d->OH, d->OW, d->ntaps, d->tdy, d->tdx, d->in_stride, d->gather, BN, MT, conv_kc_alloc(d), &g,
+                              &p->gather);
+  if (lds > 160 * 1024) refuse(PMF_E_UNSUPPORTED);
+  // 32-bit byte offsets in the epilogue (buffer stores): every tensor it touches must stay below 2 GiB
+  if ((int64_t)d->N * d->out_H * d->out_W * d->out_ldc * 4 >= (1ll << 31)) refuse(PMF_E_UNSUPPORTED);
+  if (d->ep_relu_x && (int64_t)d->N * d->out_H * d->out_W * d->ep_relu_ldc * 4 >= (1ll << 31)) refuse(PMF_E_UNSUPPORTED);
+  if (d->ep_stat_mean && (!d->stats || !d->ep_relu_x)) refuse(PMF_E_ARG);
+  if ((d->ep_flags & PMF_EP_STAT_X_ONLY) && !d->ep_stat_mean) refuse(PMF_E_ARG);
+  g.Ktot = 0;
+  int nchunks = 0;
+  for (int i = 0; i < d->nsrc; ++i) { g.Ktot += d->src[i].C; nchunks += cdiv(d->src[i].C, KC); }
+  int mode = conv_pipe_mode(d, g, p->gather, MT);
+  if (direct) {
+    mode = conv_stem_class(d) ? 14 : (d->ntaps > 1 ? 13 : 11);
+    lds = direct;
+    nchunks = 1;
+  } else if (d->w_s3 && d->in_stride == 2) {     // stride-2 3x3
+    if (MT != 1 || !conv_s3_stride2(d) || (d->ldw & 31)) refuse(PMF_E_UNSUPPORTED);
+    mode = 12;
+    nchunks = conv_stages(d, KC);
+    g.a_floats = round_up(g.in_rows * g.in_cols * (S3_APB / 4), 4);
+    lds = conv_s3_lds(g, 9, 1, BN);
+    if (lds > 160 * 1024) refuse(PMF_E_UNSUPPORTED);
+  } else if (d->w_s3 && mode == 0) {             // split-bf16 weights: the pipelined class only (pmf_conv_s3_eligible)
+    refuse(PMF_E_UNSUPPORTED);
+  } else if (d->w_s3) {
+    if (d->ldw & 31) refuse(PMF_E_UNSUPPORTED);
+    const int sl = conv_s3_slabs(d, g);
+    mode = sl == 4 ? 7 : (sl == 2 ? 6 : 5);
+    if (sl == 1 && d->ntaps == 9) mode = 8;
+    if (sl == 2 && d->ntaps == 4) mode = 10;
+    g.a_floats = sl * round_up(g.in_rows * g.in_cols * (S3_APB / 4), 4);
+    lds = conv_s3_lds(g, d->ntaps, sl, BN);
+    nchunks = conv_stages(d, KC * sl);
+    if (lds < 2 * 4 * 64 * 2 * 8) lds = 2 * 4 * 64 * 2 * 8;
+    if (lds > 160 * 1024) refuse(PMF_E_UNSUPPORTED);
+  } else {
+    if (!d->w) refuse(PMF_E_ARG);
+    if (mode == 4) {                             // 64-channel stages
+      nchunks = conv_stages(d, KC * 4);
+      lds = (g.a_floats * 4 + 4 * KC * BN) * 4;
+    }
+  }
+  if (mode == 1) g.kc_alloc = KC;   // the pipelined loop lays the weight slab out as [tap][16][BN]
+  if (d->ndst > 0 && !pmf_conv_multi_ok(d)) refuse(PMF_E_ARG);
+  const int co_tiles = cdiv(d->Cout, BN), tiles = g.tiles_x * g.tiles_y * d->N;
+  g.ksplit = d->ndst > 0 ? 1 : choose_ksplit(d, tiles * co_tiles, nchunks, force.ks);
+  g.ws = d->splitk_ws;
+  g.ws_ld = round_up(d->Cout, 4);
+  // in-kernel combine by the last-arriving workgroup of an output tile (conv_epi.h) when the caller gave a ticket array
+  p->combine = g.ksplit == 1 ? COMBINE_NONE
+             : (d->splitk_tickets != nullptr && tiles * co_tiles <= PMF_SPLITK_TICKETS ? COMBINE_TICKETS : COMBINE_FINISH);
+  g.tickets = p->combine == COMBINE_TICKETS ? d->splitk_tickets : nullptr;
+  g.one = (d->nsrc == 1 && g.ksplit == 1) ? 1 : 0;
+  p->family = mode;
+  p->nchunks = nchunks;
+  p->lds = lds;
+  p->grid = dim3(g.tiles_x * g.tiles_y, co_tiles * g.ksplit, d->N);
+  // one row per workgroup of the kernel that writes the statistics: conv_finish_k's, else one per tile and sample
+  p->stat_rows = p->combine == COMBINE_FINISH ? finish_rows(d, true) : tiles;
+  if (conv_ws_wanted(d, &p->ws)) {               // replaces the whole selection above but its K-stage count; refuses nothing
+    const WsPick& w = p->ws;
+    p->rc = 0;
+    p->family = CONV_WS; p->BN = 32 * w.nco; p->MT = 1;
+    g = w.cg;
+    p->gather = 0;
+    p->combine = COMBINE_NONE; p->stat_rows = w.rows; p->lds = w.lds;
+    p->grid = dim3(w.g.tiles_x * w.g.tiles_y, d->Cout / (32 * w.nco), d->N);
+  }
+}
+
+// number of partial-statistics rows pmf_conv_fwd writes for this descriptor (stats must hold rows*2*Cout doubles)
+extern "C" int pmf_conv_fwd_stat_rows(const pmf_conv_desc_t* d) { ConvPick p; conv_pick(d, &p); return p.stat_rows; }
+extern "C" int pmf_conv_fwd_kstages(const pmf_conv_desc_t* d) { ConvPick p; conv_pick(d, &p); return p.nchunks; }
+
+// the launch of one instantiation; the LDS opt-in once per device, the first time a launch asks for more than 64 KiB
+template <int BN, int MT, int PIPE>
+static int conv_run(const pmf_conv_desc_t* d, const ConvPick& p, hipStream_t s) {
+  static unsigned long long opted_in = 0ull;
+  if (p.lds > 64 * 1024 && pmf_first_on_device(&opted_in))
+    (void)hipFuncSetAttribute((const void*)conv_fwd_k<BN, MT, PIPE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  pmf_conv_desc_t dd = *d;
+  dd.gather = p.gather;
+  hipLaunchKernelGGL((conv_fwd_k<BN, MT, PIPE>), p.grid, dim3(256), p.lds, s, dd, p.g);
+  PMF_LAUNCH_CHECK();
+  return p.combine == COMBINE_FINISH ? pmf_conv_finish_launch(&dd, p.g, s) : 0;
+}
+
+static int conv_args(const pmf_conv_desc_t* d) {
   if (!d || d->nsrc < 1 || d->nsrc > PMF_MAX_SRC || d->ntaps < 1 || d->ntaps > PMF_MAX_TAPS) return PMF_E_ARG;
   if (d->ldw % 4 || d->in_stride < 1 || d->in_stride > 2) return PMF_E_ARG;
   for (int i = 0; i < d->nsrc; ++i)
     if (d->src[i].C % 8 || d->src[i].ldc % 4) return PMF_E_ARG;
-  if (conv_ws_wanted(d)) return pmf_conv_ws_launch(d, st);
-  int BN, MT;
-  conv_config(d, &BN, &MT);
-  if (BN == 64) return MT == 2 ? launch<64, 2>(d, s) : launch<64, 1>(d, s);
-  return MT == 2 ? launch<32, 2>(d, s) : launch<32, 1>(d, s);
+  return 0;
+}
+
+extern "C" int pmf_conv_fwd(const pmf_conv_desc_t* d, pmf_stream_t st) {
+  hipStream_t s = (hipStream_t)st;
+  if (const int rc = conv_args(d)) return rc;
+  ConvPick p;
+  conv_pick(d, &p);
+  if (p.rc) return p.rc;
+  if (p.family == CONV_WS) return conv_ws_run(d, p.ws, s);
+  // (BN, MT, PIPE) -> its instantiation; 64-channel stages (4) and the stride-2 split loop (12) exist for 128-pixel tiles only
+#define CONV_CASE(bn, mt, pipe) case bn * 1000 + mt * 100 + pipe: return conv_run<bn, mt, pipe>(d, p, s);
+#define CONV_TILE(bn, mt)                                                                                                 \
+  CONV_CASE(bn, mt, 0) CONV_CASE(bn, mt, 1) CONV_CASE(bn, mt, 5) CONV_CASE(bn, mt, 6) CONV_CASE(bn, mt, 7) CONV_CASE(bn, mt, 8) \
+  CONV_CASE(bn, mt, 10) CONV_CASE(bn, mt, 11) CONV_CASE(bn, mt, 13) CONV_CASE(bn, mt, 14)
+  switch (p.BN * 1000 + p.MT * 100 + p.family) {
+    CONV_TILE(32, 1) CONV_TILE(32, 2) CONV_TILE(64, 1) CONV_TILE(64, 2)
+    CONV_CASE(32, 1, 4) CONV_CASE(32, 1, 12) CONV_CASE(64, 1, 4) CONV_CASE(64, 1, 12)
+  }
+#undef CONV_TILE
+#undef CONV_CASE
+  return PMF_E_UNSUPPORTED;
+}
+
+// which kernel pmf_conv_fwd runs for a descriptor, and how (include/pmf_amd.h); nothing is launched
+extern "C" int pmf_conv_fwd_variant(const pmf_conv_desc_t* d, int32_t info[12]) {
+  for (int i = 0; i < 12; ++i) info[i] = 0;
+  if (const int rc = conv_args(d)) return rc;
+  ConvPick p;
+  conv_pick(d, &p);
+  const bool ws = p.family == CONV_WS;
+  const int32_t v[12] = {p.BN, p.MT, p.g.ksplit, p.combine, p.stat_rows, p.nchunks, p.lds, (int32_t)p.grid.x, (int32_t)p.grid.y,
+                         (int32_t)p.grid.z, ws ? p.ws.nco : 0, ws ? p.ws.asl : 0};
+  for (int i = 0; i < 12; ++i) info[i] = v[i];
+  return p.rc ? p.rc : p.family;
 }

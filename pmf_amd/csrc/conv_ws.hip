@@ -70,14 +70,6 @@ __device__ __forceinline__ float ws_sub(float a, float b) {
   return r;
 }
 
-struct WsGeom {
-  int segs_x_log2, th, tw, tiles_x, tiles_y;
-  int in_rows, in_cols, dy_min, dx_min;
-  int a_bytes;          // one input-tile buffer
-  int KS, CT;           // 16-channel chunks in all operands; 32-channel output tiles in the packed weights (ldw / 32)
-  int w_bytes;          // size of the packed weight array (buffer range)
-};
-
 // NTAPS taps, NCO output-channel tiles per workgroup, ASL staging slots (16 bytes) per thread, PD weight prefetch distance
 template <int NTAPS, int NCO, int ASL, int PD>
 __global__ __launch_bounds__(256) void conv_ws_k(const pmf_conv_desc_t d, const WsGeom g, const ConvGeom cg) {
@@ -362,19 +354,19 @@ static bool ws_geometry(const pmf_conv_desc_t* d, WsGeom* g, ConvGeom* cg, int* 
 }
 
 // eligibility: split-bf16 weights, 9 or 4 taps, stride 1, one halo tile of <= 1280 staging slots, operands multiples of 16
-// channels with the output's H x W, no broadcast, Cout a multiple of 32 (of 32 NCO for the chosen NCO)
+// channels with the output's H x W, no broadcast, Cout a multiple of 32 (of 32 NCO for the chosen NCO).  Strided outputs (parity
+// classes of a stride-2 input gradient) are fine: epilogue.  One pass fills everything the selection asks: geometry and rows
+// for every descriptor whose halo tile fits, NCO for the eligible ones.
 extern "C" int pmf_conv_multi_ok(const pmf_conv_desc_t* d);
-extern "C" int pmf_conv_ws_ok(const pmf_conv_desc_t* d) {
+static int ws_nco(const pmf_conv_desc_t* d, const WsPick& p) {
+  if (!p.rows) return 0;
   if (!d->w_s3 || d->in_stride != 1 || d->gather || (d->ntaps != 9 && d->ntaps != 4) || (d->ldw & 31) || (d->Cout & 31)) return 0;
-  if (d->out_sy != 1 && d->out_sy != 0) { /* strided outputs (parity classes of a stride-2 input gradient) are fine: epilogue */ }
   for (int i = 0; i < d->nsrc; ++i) {
     const pmf_src_t& s = d->src[i];
     if (s.C % 16 || (s.flags & PMF_SRC_BCAST) || s.H != d->src[0].H || s.W != d->src[0].W) return 0;
     if ((int64_t)d->N * s.H * s.W * s.ldc * 4 >= (1ll << 31)) return 0;
   }
   if (d->ndst > 0 && !pmf_conv_multi_ok(d)) return 0;     // (ranges start on 32-channel tiles and add up to Cout; no bias)
-  WsGeom g; ConvGeom cg; int asl;
-  if (!ws_geometry(d, &g, &cg, &asl)) return 0;
   if ((int64_t)d->N * d->out_H * d->out_W * d->out_ldc * 4 >= (1ll << 31)) return 0;
   int nco = d->Cout % 128 == 0 ? 4 : (d->Cout % 64 == 0 ? 2 : 1);
   // cfg bits 26-27 / PMF_CONV_WS_NCO: at most 1 / 2 / 4 tiles per workgroup; default: as many as the channel count allows while
@@ -383,45 +375,33 @@ extern "C" int pmf_conv_ws_ok(const pmf_conv_desc_t* d) {
   const int code = ((d->cfg >> 25) & 1) ? ((d->cfg >> 26) & 3) : 0;     // (bits 26-27 mean something only next to bit 25)
   const int want = code ? (1 << (code - 1)) : env_nco;
   if (want == 1 || want == 2 || want == 4) { while (nco > want) nco >>= 1; return nco; }
-  const int tiles = g.tiles_x * g.tiles_y * d->N;
-  while (nco > 1 && tiles * (d->Cout / (32 * nco)) < 256) nco >>= 1;
+  while (nco > 1 && p.rows * (d->Cout / (32 * nco)) < 256) nco >>= 1;
   return nco;
 }
-
-extern "C" int pmf_conv_ws_rows(const pmf_conv_desc_t* d) {       // partial-statistics rows of a launch (one per tile and sample)
-  WsGeom g; ConvGeom cg; int asl;
-  if (!ws_geometry(d, &g, &cg, &asl)) return 0;
-  return g.tiles_x * g.tiles_y * d->N;
+void conv_ws_pick(const pmf_conv_desc_t* d, WsPick* p) {
+  p->rows = ws_geometry(d, &p->g, &p->cg, &p->asl) ? p->g.tiles_x * p->g.tiles_y * d->N : 0;
+  p->lds = p->rows && 2 * p->g.a_bytes > 2 * 4 * 64 * 2 * 8 ? 2 * p->g.a_bytes : 2 * 4 * 64 * 2 * 8;   // (>= the statistics reduction)
+  p->nco = ws_nco(d, *p);
 }
+extern "C" int pmf_conv_ws_ok(const pmf_conv_desc_t* d) { WsPick p; conv_ws_pick(d, &p); return p.nco; }
+extern "C" int pmf_conv_ws_rows(const pmf_conv_desc_t* d) { WsPick p; conv_ws_pick(d, &p); return p.rows; }
 
-template <int NTAPS, int NCO, int PD>
-static int ws_launch_(const pmf_conv_desc_t* d, const WsGeom& g, const ConvGeom& cg, int asl, hipStream_t s) {
-  const dim3 grid(g.tiles_x * g.tiles_y, d->Cout / (32 * NCO), d->N);
-  int lds = 2 * g.a_bytes;
-  if (lds < 2 * 4 * 64 * 2 * 8) lds = 2 * 4 * 64 * 2 * 8;
-  static unsigned long long attr = 0ull;
-  if (pmf_first_on_device(&attr)) {
-    (void)hipFuncSetAttribute((const void*)conv_ws_k<NTAPS, NCO, 4, PD>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv_ws_k<NTAPS, NCO, 5, PD>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
-  if (asl == 4) hipLaunchKernelGGL((conv_ws_k<NTAPS, NCO, 4, PD>), grid, dim3(256), lds, s, *d, g, cg);
-  else hipLaunchKernelGGL((conv_ws_k<NTAPS, NCO, 5, PD>), grid, dim3(256), lds, s, *d, g, cg);
+// one instantiation: the LDS opt-in once per device, the first time a launch asks for more than 64 KiB
+template <auto K>
+static int ws_run(const pmf_conv_desc_t* d, const WsPick& p, hipStream_t s) {
+  static unsigned long long opted_in = 0ull;
+  if (p.lds > 64 * 1024 && pmf_first_on_device(&opted_in))
+    (void)hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  hipLaunchKernelGGL(K, dim3(p.g.tiles_x * p.g.tiles_y, d->Cout / (32 * p.nco), d->N), dim3(256), p.lds, s, *d, p.g, p.cg);
   PMF_LAUNCH_CHECK();
   return 0;
 }
 
-extern "C" int pmf_conv_ws_launch(const pmf_conv_desc_t* d, pmf_stream_t st) {
-  hipStream_t s = (hipStream_t)st;
-  const int nco = pmf_conv_ws_ok(d);
-  if (!nco) return PMF_E_UNSUPPORTED;
-  WsGeom g; ConvGeom cg; int asl;
-  ws_geometry(d, &g, &cg, &asl);
-  if (d->ntaps == 9) {
-    if (nco == 4) return ws_launch_<9, 4, 2>(d, g, cg, asl, s);
-    if (nco == 2) return ws_launch_<9, 2, 2>(d, g, cg, asl, s);
-    return ws_launch_<9, 1, 8>(d, g, cg, asl, s);
-  }
-  if (nco == 4) return ws_launch_<4, 4, 1>(d, g, cg, asl, s);
-  if (nco == 2) return ws_launch_<4, 2, 3>(d, g, cg, asl, s);
-  return ws_launch_<4, 1, 3>(d, g, cg, asl, s);
+int conv_ws_run(const pmf_conv_desc_t* d, const WsPick& p, hipStream_t s) {
+#define WS_CASE(T, NC, PD)                                                                                \
+  if (d->ntaps == T && p.nco == NC)                                                                       \
+    return p.asl == 4 ? ws_run<conv_ws_k<T, NC, 4, PD>>(d, p, s) : ws_run<conv_ws_k<T, NC, 5, PD>>(d, p, s)
+  WS_CASE(9, 4, 2); WS_CASE(9, 2, 2); WS_CASE(9, 1, 8); WS_CASE(4, 4, 1); WS_CASE(4, 2, 3); WS_CASE(4, 1, 3);
+#undef WS_CASE
+  return PMF_E_UNSUPPORTED;
 }

@@ -47,6 +47,17 @@ CONV_CASES = [
 ]
 
 
+def _nan_rows(n, Cout):
+    return torch.full((n, 2, Cout), float("nan"), device="cuda", dtype=torch.float64)
+
+
+def _written_rows(stats, rows):
+    """the first ``rows`` rows of a _nan_rows(rows + 2) buffer after a launch; the two guard rows behind them must still hold
+    the NaN bit pattern they were filled with (a launch that writes more rows than pmf_conv_fwd_stat_rows said)"""
+    assert torch.equal(stats[rows:].view(torch.int64), _nan_rows(2, stats.shape[2]).view(torch.int64))
+    return stats[:rows]
+
+
 @pytest.mark.parametrize("case", CONV_CASES, ids=[c[0] for c in CONV_CASES])
 def test_conv_fwd_vs_torch_cpu(case):
     name, N, H, W, cins, Cout, k, dil, pad, stride, act, xf = case
@@ -78,12 +89,12 @@ def test_conv_fwd_vs_torch_cpu(case):
     b_dev = b.cuda()   # keep alive: the descriptor only holds raw pointers
     d = G.conv_desc(srcs, wpk, ldw, b_dev, out, N, OH, OW, Cout, G.taps_of(k, k, dil, pad), stride, act)
     rows = lib.pmf_conv_fwd_stat_rows(C.byref(d))          # one partial (sum, sumsq) row per workgroup tile
-    stats = torch.full((rows, 2, Cout), float("nan"), device="cuda", dtype=torch.float64)
+    stats = _nan_rows(rows + 2, Cout)                        # exactly `rows` rows are written: two guard rows behind them
     d.stats = stats.data_ptr()
     _sync_check(lib.pmf_conv_fwd(C.byref(d), G.stream()), "pmf_conv_fwd")
     got = G.from_nhwc(out, Cout)
     assert G.rel_err(got.numpy(), ref.numpy()) < 2e-5
-    st = stats.sum(0).cpu()
+    st = _written_rows(stats, rows).sum(0).cpu()
     assert torch.isfinite(st).all()
     assert G.rel_err(st[0].numpy() / ref[0, 0].numel(), (ref.sum((0, 2, 3)) / ref[0, 0].numel()).numpy()) < 1e-3
     assert G.rel_err(st[1].numpy() / ref[0, 0].numel(), ((ref * ref).sum((0, 2, 3)) / ref[0, 0].numel()).numpy()) < 1e-3
@@ -142,12 +153,12 @@ def test_conv_fwd_split_bf16_vs_float64(case, cfg):
             d.w, d.w_s3 = None, wpk.data_ptr()
             assert lib.pmf_conv_s3_eligible(C.byref(d)) == (3 if stem else (2 if k == 1 else 1))   # 2: direct 1x1, 3: stem
         rows = lib.pmf_conv_fwd_stat_rows(C.byref(d))
-        stats = torch.full((rows, 2, Cout), float("nan"), device="cuda", dtype=torch.float64)
+        stats = _nan_rows(rows + 2, Cout)
         d.stats = stats.data_ptr()
         _sync_check(lib.pmf_conv_fwd(C.byref(d), G.stream()), "pmf_conv_fwd")
         got = G.from_nhwc(out, Cout).double()
         errs[kind] = float((got - ref).abs().max() / ref.abs().max())
-        st = stats.sum(0).cpu()
+        st = _written_rows(stats, rows).sum(0).cpu()
         assert torch.isfinite(st).all()
         assert G.rel_err(st[0].numpy() / ref[0, 0].numel(), (ref.sum((0, 2, 3)) / ref[0, 0].numel()).numpy()) < 1e-5
         if ((cfg >> 16) & 255) > 1 and not (cfg >> 24):
@@ -160,11 +171,11 @@ def test_conv_fwd_split_bf16_vs_float64(case, cfg):
             outs = []
             for rep in range(3):
                 out_t = torch.zeros_like(out)
-                stats_t = torch.full((rows_t, 2, Cout), float("nan"), device="cuda", dtype=torch.float64)
+                stats_t = _nan_rows(rows_t + 2, Cout)
                 d.out, d.stats = out_t.data_ptr(), stats_t.data_ptr()
                 _sync_check(lib.pmf_conv_fwd(C.byref(d), G.stream()), "pmf_conv_fwd (tickets)")
                 assert int(tk.abs().sum()) == 0
-                outs.append((out_t, stats_t))
+                outs.append((out_t, _written_rows(stats_t, rows_t)))
             got_t = G.from_nhwc(outs[0][0], Cout).double()
             e_t = float((got_t - ref).abs().max() / ref.abs().max())
             assert e_t < 2e-6 and e_t <= 4 * errs["f32"] + 1e-7, (kind, e_t, errs)

@@ -14,9 +14,9 @@ def build():
     if os.environ.get("TRACE_LIB"):          # a prebuilt private copy (experiments)
         return C.CDLL(os.environ["TRACE_LIB"])
     so = "/tmp/libpmf_conv_trace.so"
-    src = os.path.join(ROOT, "pmf_amd/csrc/conv_fwd.hip")
+    srcs = [os.path.join(ROOT, "pmf_amd/csrc", f) for f in ("conv_fwd.hip", "conv_ws.hip")]     # (the selection asks conv_ws.hip)
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
-                           "-munsafe-fp-atomics", "-mllvm", "-amdgpu-mfma-vgpr-form", "-DPMF_CONV_TRACE", src, "-o", so])
+                           "-munsafe-fp-atomics", "-mllvm", "-amdgpu-mfma-vgpr-form", "-DPMF_CONV_TRACE"] + srcs + ["-o", so])
     return C.CDLL(so)
 
 def main(filt, with_stats):
@@ -56,8 +56,12 @@ def main(filt, with_stats):
         span = en.max() - t0
         # s_memtime frequency: calibrate against wall clock over the END stamps
         f = (en.max() - en.min()) / max(wall, 1) * 100.0 if wall > 0 else float("nan")   # MHz
-        print("== %s: %d workgroups, %d stamps each, launch span %d ticks (s_memtime ~%.0f MHz -> %.1f us)" %
-              (name, nwg, cnt, span, f, span / f if f == f else 0))
+        info = (C.c_int32 * 12)()
+        variant = L.lib().pmf_conv_fwd_variant(C.byref(d), C.byref(info))
+        print("== %s [%s, BN %d, MT %d, ksplit %d, combine %d, %d stat rows, %d K stages, LDS %d, grid %d x %d x %d]: %d workgroups, "
+              "%d stamps each, launch span %d ticks (s_memtime ~%.0f MHz -> %.1f us)" %
+              ((name, "conv_ws_k NCO %d ASL %d" % (info[10], info[11]) if variant == L.CONV_WS_FAMILY else "PIPE %d" % variant) +
+               tuple(info[:10]) + (nwg, cnt, span, f, span / f if f == f else 0)))
         xcc = t[:, 61] & 0xf; cu = (t[:, 62] >> 8) & 0xf; se = (t[:, 62] >> 13) & 0x7; sh = (t[:, 62] >> 12) & 1
         print("   start offset: median %d, p90 %d, max %d ticks;  end offset: min %d median %d" %
               (np.median(st_ - t0), np.percentile(st_ - t0, 90), (st_ - t0).max(), (en - t0).min(), np.median(en - t0)))
