@@ -690,6 +690,34 @@ int pmf_eval_range_batch(const float* prob, int32_t B, int32_t C, int32_t H, int
                          const int32_t* py, const float* unproj_range, const int32_t* sem, const int32_t* lut, int32_t nlut,
                          int32_t knn, int32_t search, const float* inv_gauss, float cutoff, int32_t* argmax_ws,
                          int32_t* labels, int64_t* pixel_conf, int64_t* point_conf, pmf_stream_t s);
+/* ---- PMF evaluation on SensatUrban bird's-eye-view frames (tasks/sensat_urban/pmf_eval/infer.py:95-208) -----------------
+ * A frame is f32[8][h][w] on the device (the file's float64 converted on the host, the reference's .float()); it is cut into
+ * S x S tiles, S a multiple of 16.  origins: HOST array int32[T][2] of (h_start, w_start), 1 <= T <= 64, every origin inside
+ * the frame; a tile may run past h or w (a frame smaller than S, origin 0).  V = 1 (the tile) or 6 (+ five variants of the
+ * same size, in the reference's order: v1 rot90(1,(H,W)): out[i][j] = in[j][S-1-i], v2 rot90(2), v3 flip along W, v4 flip
+ * along H, v5 transpose); batch element order tile-major, variant-minor.
+ * pmf_bev_tile_pre: per pixel of a tile the frame value (0 past h or w: the reference's zero-initialised crop), then
+ * (x - mean[c]) / stds[c] * mask in fp32 in exactly this order, mask = the un-normalised channel 4 of the pixel; channels
+ * 0-4 -> pcd f32[T*V][5][S][S], 5-7 -> rgb f32[T*V][3][S][S].  pcd_pad / rgb_pad (both or neither): f32[T][5|3][S+32][S+32],
+ * v0 inside a 16-pixel border of exact zeros. */
+int pmf_bev_tile_pre(const float* frame, int32_t h, int32_t w, const float* mean, const float* stds, const int32_t* origins,
+                     int32_t T, int32_t S, int32_t V, float* pcd, float* rgb, float* pcd_pad, float* rgb_pad,
+                     pmf_stream_t s);
+/* pmf_bev_tile_accum: prob f32[T*V][C][S][S], prob_pad (optional, V = 6 only) f32[T][C][S+32][S+32]; conf_map f32[C][h][w]
+ * updated in place.  Per tile in list order (one launch each, stream order: overlapping tiles add in list order, no
+ * atomics) and per pixel of the min(S, h - h_start) x min(S, w - w_start) top-left part of the tile (the part the frame
+ * filled; the reference raises on a frame smaller than the tile): every variant undone (v1 by rot90(3), v2 by rot90(2), v3 /
+ * v4 by the same flips, v5 by a transpose, the padded one by the centre crop [16:16+S]) and summed in fp32 in the
+ * reference's order ((((((p0 + d1) + d2) + d3) + d4) + d5) + d6), the sum added to the map.  V = 1: only p0. */
+int pmf_bev_tile_accum(const float* prob, const float* prob_pad, int32_t C, const int32_t* origins, int32_t T, int32_t S,
+                       int32_t V, float* conf_map, int32_t h, int32_t w, pmf_stream_t s);
+/* pmf_bev_points: per point p: pred = pred_in[p] (optional int64[P]: the class already voted by KNN), else
+ * class_map[h_idx[p]][w_idx[p]] (int32[h][w], int64 indices; outside the map -> 0); pred == 0 -> 1 and *n_zero (optional
+ * int64 on the device) += 1; conf (optional, needs label uint8[P], C <= 64) int64[C][C] += (pred, (uint8)(label + 1)),
+ * targets >= C not counted; out uint8[P] = pred - 1.  P == 0 is a no-op. */
+int pmf_bev_points(const int32_t* class_map, int32_t h, int32_t w, const int64_t* h_idx, const int64_t* w_idx, int64_t P,
+                   const int64_t* pred_in, const uint8_t* label, int32_t C, int64_t* conf, int64_t* n_zero, uint8_t* out,
+                   pmf_stream_t s);
 /* pixel splits pmf_conv_wgrad will use for this descriptor (sizes `partial`) */
 int pmf_conv_wgrad_nsplit(const pmf_wgrad_desc_t* d);
 /* the kernel family pmf_conv_wgrad runs for this descriptor under the current PMF_WG_* switches (the same selection that
