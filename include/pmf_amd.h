@@ -718,6 +718,41 @@ int pmf_bev_tile_accum(const float* prob, const float* prob_pad, int32_t C, cons
 int pmf_bev_points(const int32_t* class_map, int32_t h, int32_t w, const int64_t* h_idx, const int64_t* w_idx, int64_t P,
                    const int64_t* pred_in, const uint8_t* label, int32_t C, int64_t* conf, int64_t* n_zero, uint8_t* out,
                    pmf_stream_t s);
+/* ---- SensatUrban dataset preparation: points of a block -> bird's-eye-view frame (csrc/bev_prepare.hip; the reference's
+ * tasks/sensat_urban/dataset_prepare/compute_bev_feature.py) ------------------------------------------------------------------
+ * x y z: float32[P] on the device, red green blue: uint8[P], label: uint8[P] or NULL (the test split: class 0).  Pixel of a
+ * point: h_idx = int32(trunc((y - min y) / grid)), w_idx likewise from x; f64 = 0: float32 subtraction and correctly rounded
+ * float32 division by (float)grid (numpy's promotion on the labelled splits), f64 = 1: both in float64 (the test split).
+ * h = max h_idx + 1, w = max w_idx + 1.  Per cell, over its points in ascending point index: channel 0 max z, 1 min z,
+ * 2 the float64 sum of z in that order / (count + 1e-6), 3 log10_tab[count + 1], 4 1, 5-7 and label_map the colour and class
+ * of the first point that attains the maximum; empty cells 0 and label -1.  Every value equals the reference's loop bit for
+ * bit; the results do not depend on the order in which the device runs anything.
+ * Call order on one stream: extent -> (read *ext on the host: flags, h, w) -> bin -> scan -> place -> (read ext->max_count,
+ * fill log10_tab[k] = log10(k) for k < tab_n with numpy, tab_n >= max_count + 2) -> cells -> (read ext->flags once more).
+ * All entry points return PMF_E_ARG without a launch for a NULL pointer, P == 0, P >= 2^31 - 1, grid <= 0 or not finite,
+ * h or w < 1 and h * w > 2^31 - 2 (cells are indexed in int32). */
+#define PMF_BEV_NONFINITE 1   /* ext->flags: a non-finite x, y or z (nothing further may be launched) */
+#define PMF_BEV_RANGE 2       /* ... an extent of 2^31 - 2 cells or more along one axis */
+#define PMF_BEV_INTERNAL 4    /* ... a point outside the extent or a slot outside its cell: not reachable, never written */
+typedef struct {
+  float min_x, min_y, max_x, max_y;
+  int32_t h, w, flags, max_count;
+} pmf_bev_extent_t;
+/* bytes of `workspace`: (P, 0, 0) for pmf_bev_prepare_extent, (P, h, w) for the later stages (one buffer of the larger size
+ * may serve both); negative = argument error */
+int64_t pmf_bev_prepare_workspace(int64_t P, int64_t h, int64_t w);
+int pmf_bev_prepare_extent(const float* x, const float* y, const float* z, int64_t P, double grid, int32_t f64,
+                           void* workspace, pmf_bev_extent_t* ext, pmf_stream_t s);
+/* h_idx / w_idx int32[P] written; the cell counts go to the workspace */
+int pmf_bev_prepare_bin(const float* x, const float* y, int64_t P, double grid, int32_t f64, pmf_bev_extent_t* ext, int32_t h,
+                        int32_t w, void* workspace, int32_t* h_idx, int32_t* w_idx, pmf_stream_t s);
+int pmf_bev_prepare_scan(int64_t P, int32_t h, int32_t w, void* workspace, pmf_bev_extent_t* ext, pmf_stream_t s);
+int pmf_bev_prepare_place(const int32_t* h_idx, const int32_t* w_idx, int64_t P, int32_t h, int32_t w, void* workspace,
+                          pmf_bev_extent_t* ext, pmf_stream_t s);
+/* feature_map f64[8][h][w], label_map f64[h][w]: every element written.  max_count: the value read from ext (1..P) */
+int pmf_bev_prepare_cells(const float* z, const uint8_t* red, const uint8_t* green, const uint8_t* blue, const uint8_t* label,
+                          int64_t P, int32_t h, int32_t w, void* workspace, const double* log10_tab, int64_t tab_n,
+                          int64_t max_count, double* feature_map, double* label_map, pmf_stream_t s);
 /* pixel splits pmf_conv_wgrad will use for this descriptor (sizes `partial`) */
 int pmf_conv_wgrad_nsplit(const pmf_wgrad_desc_t* d);
 /* the kernel family pmf_conv_wgrad runs for this descriptor under the current PMF_WG_* switches (the same selection that

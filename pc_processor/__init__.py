@@ -11,3 +11,4 @@ _sys.modules["pc_processor.dataset.semantic_kitti.parser"] = dataset.semantic_ki
 _sys.modules["pc_processor.dataset.preprocess.augmentor"] = dataset.preprocess.augmentor
 _sys.modules["pc_processor.dataset.preprocess.projection"] = dataset.preprocess.projection
 _sys.modules["pc_processor.dataset.sensat_urban.sensat_urban"] = dataset.sensat_urban.sensat_urban
+_sys.modules["pc_processor.dataset.sensat_urban.prepare"] = dataset.sensat_urban.prepare

@@ -17,6 +17,7 @@ WGRAD_S3 = 1
 # pmf_conv_wgrad_variant (PMF_WG_*)
 WG_UNIT, WG_PIPE, WG_STAGED, WG_SWP, WG_W8, WG_NSPLIT, WG_DIRECT, WG_DIRECT_S3, WG_STREAM, WG_FEWC = range(10)
 PMF_E_ARG, PMF_E_UNSUPPORTED = -1, -2
+BEV_NONFINITE, BEV_RANGE, BEV_INTERNAL = 1, 2, 4   # pmf_bev_extent_t.flags (PMF_BEV_*)
 CFG_DIRECT_TAPS = 1 << 24      # pmf_conv_desc_t.cfg: direct multi-tap variant (PMF_CFG_DIRECT_TAPS)
 CFG_WS = 1 << 25               # ... the wave-scheduled N-split kernel (PMF_CFG_WS, csrc/conv_ws.hip)
 CONV_WS_FAMILY = 100           # pmf_conv_fwd_variant: conv_ws_k (PMF_CONV_WS_FAMILY); otherwise the PIPE of conv_fwd_k
@@ -337,6 +338,22 @@ def lib():
     L.pmf_bev_points.restype = C.c_int
     L.pmf_bev_points.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                  C.c_int32] + [C.c_void_p] * 4
+    L.pmf_bev_prepare_workspace.restype = C.c_int64
+    L.pmf_bev_prepare_workspace.argtypes = [C.c_int64, C.c_int64, C.c_int64]
+    L.pmf_bev_prepare_extent.restype = C.c_int
+    L.pmf_bev_prepare_extent.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int32, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]
+    L.pmf_bev_prepare_bin.restype = C.c_int
+    L.pmf_bev_prepare_bin.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pmf_bev_prepare_scan.restype = C.c_int
+    L.pmf_bev_prepare_scan.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pmf_bev_prepare_place.restype = C.c_int
+    L.pmf_bev_prepare_place.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]
+    L.pmf_bev_prepare_cells.restype = C.c_int
+    L.pmf_bev_prepare_cells.argtypes = [C.c_void_p] * 5 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                                           C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -348,7 +365,7 @@ EXPORTS = [
     "pmf_maxpool3s2_bwd", "pmf_bilinear2x", "pmf_bilinear2x_bwd", "pmf_pixel_shuffle2", "pmf_pixel_shuffle2_bwd",
     "pmf_fusion_gate", "pmf_fusion_gate_bwd", "pmf_global_mean", "pmf_global_mean_bwd", "pmf_broadcast_rows", "pmf_colsum", "pmf_colsum_rows",
     "pmf_pmask_from", "pmf_pmask_pool", "pmf_pmask_mul", "pmf_pmask_mul_bwd", "pmf_vec_add", "pmf_softmax_nhwc_to_nchw", "pmf_softmax_bwd_nchw_to_nhwc", "pmf_logits_nhwc_to_nchw", "pmf_logits_bwd_nchw_to_nhwc", "pmf_nchw_to_nhwc", "pmf_fill", "pmf_debug_col", "pmf_bn_bwd_small_ok", "pmf_bn_bwd_small", "pmf_knn_vote", "pmf_knn_vote_batch", "pmf_knn_vote_batch_prob", "pmf_merge_pred", "pmf_merge_pred_fallback",
-    "pmf_project_scatter", "pmf_project_scatter2", "pmf_project_v2_index", "pmf_project_v2_index_scaled", "pmf_project_v2_scatter", "pmf_points_transform", "pmf_range_project_index", "pmf_range_project_gather", "pmf_crop_pad", "pmf_flip_rotate_crop", "pmf_color_jitter", "pmf_lovasz_grad", "pmf_loss_rows", "pmf_loss_chunks", "pmf_loss_pixel", "pmf_loss_lovasz", "pmf_loss_pixel_w", "pmf_loss_lovasz_w", "pmf_loss_sort_workspace", "pmf_loss_lovasz_sort", "pmf_loss_lovasz_sort_w", "pmf_plan_run", "pmf_plan_run_range", "pmf_plan_capture", "pmf_graph_launch", "pmf_graph_destroy", "pmf_plan_lanes", "pmf_plan_issue_order", "pmf_graph_pieces", "pmf_plan_event_wait", "pmf_adamw_range", "pmf_sgd_range", "pmf_normalise_inplace", "pmf_eval_pre", "pmf_eval_argmax", "pmf_eval_points", "pmf_eval_view_merge", "pmf_eval_sweep_finish", "pmf_eval_range_batch", "pmf_eval_fill", "pmf_eval_sweep_finish_fill", "pmf_bev_tile_pre", "pmf_bev_tile_accum", "pmf_bev_points", "pmf_sizeof", "pmf_version", "pmf_conv_multi_ok",
+    "pmf_project_scatter", "pmf_project_scatter2", "pmf_project_v2_index", "pmf_project_v2_index_scaled", "pmf_project_v2_scatter", "pmf_points_transform", "pmf_range_project_index", "pmf_range_project_gather", "pmf_crop_pad", "pmf_flip_rotate_crop", "pmf_color_jitter", "pmf_lovasz_grad", "pmf_loss_rows", "pmf_loss_chunks", "pmf_loss_pixel", "pmf_loss_lovasz", "pmf_loss_pixel_w", "pmf_loss_lovasz_w", "pmf_loss_sort_workspace", "pmf_loss_lovasz_sort", "pmf_loss_lovasz_sort_w", "pmf_plan_run", "pmf_plan_run_range", "pmf_plan_capture", "pmf_graph_launch", "pmf_graph_destroy", "pmf_plan_lanes", "pmf_plan_issue_order", "pmf_graph_pieces", "pmf_plan_event_wait", "pmf_adamw_range", "pmf_sgd_range", "pmf_normalise_inplace", "pmf_eval_pre", "pmf_eval_argmax", "pmf_eval_points", "pmf_eval_view_merge", "pmf_eval_sweep_finish", "pmf_eval_range_batch", "pmf_eval_fill", "pmf_eval_sweep_finish_fill", "pmf_bev_tile_pre", "pmf_bev_tile_accum", "pmf_bev_points", "pmf_bev_prepare_workspace", "pmf_bev_prepare_extent", "pmf_bev_prepare_bin", "pmf_bev_prepare_scan", "pmf_bev_prepare_place", "pmf_bev_prepare_cells", "pmf_sizeof", "pmf_version", "pmf_conv_multi_ok",
 ]
 
 

@@ -1,1 +1,2 @@
 from .sensat_urban import SensatUrban, tile_windows  # noqa: F401
+from .prepare import compute_bev_feature  # noqa: F401
