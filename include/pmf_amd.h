@@ -527,6 +527,23 @@ int pmf_loss_lovasz_sort(const float* key, const int64_t* label, int32_t N, int3
 int pmf_loss_lovasz_sort_w(const float* key, const int64_t* label, int32_t N, int32_t C, int64_t HW,
                            const unsigned long long* cnt, const float* w6, void* workspace, float* bsum, double* dots,
                            const double* rows, float* grad_lidar, float* grad_camera, float* out8, pmf_stream_t s);
+/* The SensatUrban objective (tasks/sensat_urban/pmf/trainer.py:205-216, 296-318): the PMF objective plus
+ * ExpLogDiceLoss()(prob, label, mask = label > 0) per head (pc_processor/loss/dice_loss.py):
+ *   dice_c = (2 I_c + 1e-6) / (S_c + T_c + 1e-6) over the labelled pixels (T = the label histogram cnt, T_0 = unlabelled
+ *   pixels), L = (-ln max(mean_c dice_c, 1e-6))^0.3.
+ * pmf_loss_pixel_dice = pmf_loss_pixel with a pre-pass: the histogram stage also sums both probability maps at labelled
+ *   pixels (parts f64[pmf_loss_dice_parts(P)][4C] scratch, float64, fixed order, no atomics on floats), one workgroup folds
+ *   them into dice f64[2][2 + 2C] = per head {L, K/C, dice_c[C], 1/D_c[C]}, and the per-pixel kernel adds
+ *   dL/dx_c = K/C (2 [t = c] - dice_c) / D_c at labelled pixels to grad_* in registers.
+ * Then pmf_loss_lovasz_sort as for the PMF objective, with a 10-float output vector, and pmf_loss_dice_finish:
+ *   out10 = {total + dice + dice_cam, foc, lov, foc_cam, lov_cam, per, per_p, per_q, dice, dice_cam}. */
+int pmf_loss_dice_parts(int64_t P);
+int pmf_loss_pixel_dice(const float* lidar_prob, const float* camera_prob, const int64_t* label, const float* alpha,
+                        int32_t N, int32_t C, int64_t HW, float focal_gamma, float tau, float gamma_per,
+                        unsigned long long* cnt, float* grad_lidar, float* grad_camera, float* key, double* rows,
+                        unsigned long long* conf_lidar, unsigned long long* conf_camera, double* parts, double* dice,
+                        pmf_stream_t s);
+int pmf_loss_dice_finish(const double* dice, int32_t C, float* out10, pmf_stream_t s);
 
 /* ---- plan executor: a whole forward (or backward) pass = one call --------------------------------------- */
 enum {
@@ -598,6 +615,11 @@ int pmf_adamw_range(float* param, const float* grad, float* exp_avg, float* exp_
                     double beta1, double beta2, double eps, double weight_decay, const float* step, pmf_stream_t s);
 int pmf_sgd_range(float* param, const float* grad, float* momentum_buffer, int64_t n, double lr, double momentum,
                   double dampening, double weight_decay, int32_t nesterov, int32_t first_step, pmf_stream_t s);
+/* torch.optim.AdamW(amsgrad=True) (tasks/sensat_urban/pmf/trainer.py:83-84): pmf_adamw_range with the running maximum
+ * max_exp_avg_sq = max(max_exp_avg_sq, exp_avg_sq) in the denominator.  A null max_exp_avg_sq or step is PMF_E_ARG. */
+int pmf_adamw_amsgrad_range(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq,
+                            int64_t n, double lr, double beta1, double beta2, double eps, double weight_decay,
+                            const float* step, pmf_stream_t s);
 /* Replaces the four element-wise passes of tasks/pmf/trainer.py:291-295 (tasks/epmf/trainer.py likewise):
  *   input_feature[:, 0:C] = (input_feature[:, 0:C] - mean) / std * mask.unsqueeze(1)      in place, one launch.
  * x: [N, >= C, H, W] float32 with contiguous channel planes, stride_n floats between samples (8 * HW for the 8-channel

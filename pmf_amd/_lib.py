@@ -266,6 +266,15 @@ def lib():
     L.pmf_loss_lovasz_sort_w.restype = C.c_int
     L.pmf_loss_lovasz_sort_w.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p] + \
         [C.c_void_p] * 8
+    L.pmf_loss_dice_parts.restype = C.c_int
+    L.pmf_loss_dice_parts.argtypes = [C.c_int64]
+    L.pmf_loss_pixel_dice.restype = C.c_int
+    L.pmf_loss_pixel_dice.argtypes = [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_int64, C.c_float, C.c_float, C.c_float] + \
+        [C.c_void_p] * 10
+    L.pmf_loss_dice_finish.restype = C.c_int
+    L.pmf_loss_dice_finish.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    L.pmf_adamw_amsgrad_range.restype = C.c_int
+    L.pmf_adamw_amsgrad_range.argtypes = [C.c_void_p] * 5 + [C.c_int64] + [C.c_double] * 5 + [C.c_void_p, C.c_void_p]
     L.pmf_fill.restype = C.c_int
     L.pmf_fill.argtypes = [C.c_void_p, C.c_float, C.c_int64, C.c_void_p]
     # csrc/elementwise.hip: p = pointer, i = int32, q = int64, v = const pmf_view_t*; every signature ends with the stream
@@ -366,6 +375,7 @@ EXPORTS = [
     "pmf_fusion_gate", "pmf_fusion_gate_bwd", "pmf_global_mean", "pmf_global_mean_bwd", "pmf_broadcast_rows", "pmf_colsum", "pmf_colsum_rows",
     "pmf_pmask_from", "pmf_pmask_pool", "pmf_pmask_mul", "pmf_pmask_mul_bwd", "pmf_vec_add", "pmf_softmax_nhwc_to_nchw", "pmf_softmax_bwd_nchw_to_nhwc", "pmf_logits_nhwc_to_nchw", "pmf_logits_bwd_nchw_to_nhwc", "pmf_nchw_to_nhwc", "pmf_fill", "pmf_debug_col", "pmf_bn_bwd_small_ok", "pmf_bn_bwd_small", "pmf_knn_vote", "pmf_knn_vote_batch", "pmf_knn_vote_batch_prob", "pmf_merge_pred", "pmf_merge_pred_fallback",
     "pmf_project_scatter", "pmf_project_scatter2", "pmf_project_v2_index", "pmf_project_v2_index_scaled", "pmf_project_v2_scatter", "pmf_points_transform", "pmf_range_project_index", "pmf_range_project_gather", "pmf_crop_pad", "pmf_flip_rotate_crop", "pmf_color_jitter", "pmf_lovasz_grad", "pmf_loss_rows", "pmf_loss_chunks", "pmf_loss_pixel", "pmf_loss_lovasz", "pmf_loss_pixel_w", "pmf_loss_lovasz_w", "pmf_loss_sort_workspace", "pmf_loss_lovasz_sort", "pmf_loss_lovasz_sort_w", "pmf_plan_run", "pmf_plan_run_range", "pmf_plan_capture", "pmf_graph_launch", "pmf_graph_destroy", "pmf_plan_lanes", "pmf_plan_issue_order", "pmf_graph_pieces", "pmf_plan_event_wait", "pmf_adamw_range", "pmf_sgd_range", "pmf_normalise_inplace", "pmf_eval_pre", "pmf_eval_argmax", "pmf_eval_points", "pmf_eval_view_merge", "pmf_eval_sweep_finish", "pmf_eval_range_batch", "pmf_eval_fill", "pmf_eval_sweep_finish_fill", "pmf_bev_tile_pre", "pmf_bev_tile_accum", "pmf_bev_points", "pmf_bev_prepare_workspace", "pmf_bev_prepare_extent", "pmf_bev_prepare_bin", "pmf_bev_prepare_scan", "pmf_bev_prepare_place", "pmf_bev_prepare_cells", "pmf_sizeof", "pmf_version", "pmf_conv_multi_ok",
+    "pmf_loss_dice_parts", "pmf_loss_pixel_dice", "pmf_loss_dice_finish", "pmf_adamw_amsgrad_range",
 ]
 
 

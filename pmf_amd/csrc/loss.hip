@@ -152,8 +152,12 @@ struct LossPixelArgs {
   int C;
   float fgamma, tau, gamma_per;
   const float* w6;                           // device weights {foc_l, lov_l, foc_c, lov_c, per_p, per_q} or null
+  const double* dice;                        // [2][2 + 2C] per head {L, K/C, dice_c[C], 1/D_c[C]} (loss_dice_fold_k) or null
 };
 
+// DICE: add the exp-log Dice gradient of both heads (a.dice, see loss_dice_fold_k) at labelled pixels; the <false>
+// instantiation is the kernel as it was before the Dice term existed
+template <bool DICE>
 __global__ __launch_bounds__(LP_BLOCK) void loss_pixel_k(const LossPixelArgs a) {
   __shared__ double red[4][LP_BLOCK];
   __shared__ unsigned int hist[2][LP_MAXC * LP_MAXC];
@@ -219,6 +223,9 @@ __global__ __launch_bounds__(LP_BLOCK) void loss_pixel_k(const LossPixelArgs a) 
     float* gc = a.gc + n * C * a.HW + hw;
     // d(w_pcd Lq)/dd = Lq gate_p and d(w_img Lp)/dd = -Lp gate_q through the (not detached) weights
     const bool lov_valid = t != 0;                  // Lovasz ignore label 0
+    const double* dl = a.dice;
+    const double* dq = DICE ? a.dice + 2 + 2 * C : nullptr;
+    const float kd_l = DICE && valid ? (float)dl[1] : 0.f, kd_c = DICE && valid ? (float)dq[1] : 0.f;
 #pragma unroll 4
     for (int c = 0; c < C; ++c) {
       const float pv = p[c], qv = q[c];
@@ -231,6 +238,11 @@ __global__ __launch_bounds__(LP_BLOCK) void loss_pixel_k(const LossPixelArgs a) 
       float g2 = spa * (w_img * (logf(fmaxf(qv, 1e-38f)) + 1.f - plog) - Lp * gate_q * ddq) +
                  spb * (-w_pcd * pv * (iq > 0.f ? 1.f / qv : 0.f) + Lq * gate_p * ddq);
       if (c == t) { g1 += dfl; g2 += dfc; }
+      if (DICE && valid) {       // dL/dx_c = K/C (2 [t = c] - dice_c) / D_c
+        const float two = c == t ? 2.f : 0.f;
+        g1 += kd_l * (two - (float)dl[2 + c]) * (float)dl[2 + C + c];
+        g2 += kd_c * (two - (float)dq[2 + c]) * (float)dq[2 + C + c];
+      }
       gl[c * a.HW] = g1;
       gc[c * a.HW] = g2;
       const float fg = (lov_valid && c == t) ? 1.f : 0.f;
@@ -475,8 +487,8 @@ static int loss_pixel_impl(const float* lidar_prob, const float* camera_prob, co
   LossPixelArgs a;
   a.pl = lidar_prob; a.pc = camera_prob; a.label = label; a.alpha = alpha; a.cnt = cnt;
   a.gl = grad_lidar; a.gc = grad_camera; a.key = key; a.rows = rows; a.conf_l = conf_lidar; a.conf_c = conf_camera;
-  a.HW = HW; a.P = P; a.C = C; a.fgamma = focal_gamma; a.tau = tau; a.gamma_per = gamma_per; a.w6 = w6;
-  hipLaunchKernelGGL(loss_pixel_k, dim3((unsigned)cdiv64(P, LP_BLOCK)), dim3(LP_BLOCK), 0, st, a);
+  a.HW = HW; a.P = P; a.C = C; a.fgamma = focal_gamma; a.tau = tau; a.gamma_per = gamma_per; a.w6 = w6; a.dice = nullptr;
+  hipLaunchKernelGGL(loss_pixel_k<false>, dim3((unsigned)cdiv64(P, LP_BLOCK)), dim3(LP_BLOCK), 0, st, a);
   PMF_LAUNCH_CHECK();
   return 0;
 }
@@ -494,6 +506,164 @@ extern "C" int pmf_loss_pixel_w(const float* lidar_prob, const float* camera_pro
   if (!w6) return PMF_E_ARG;
   return loss_pixel_impl(lidar_prob, camera_prob, label, alpha, N, C, HW, focal_gamma, tau, 0.f, w6, cnt, grad_lidar,
                          grad_camera, key, rows, conf_lidar, conf_camera, s);
+}
+
+// ---- exp-log Dice term of the SensatUrban objective (pc_processor/loss/dice_loss.py; tasks/sensat_urban/pmf/trainer.py:
+// 205-216: loss_foc = focal + ExpLogDiceLoss()(pred, label, mask = label > 0), both heads) --------------------------------
+// With m_i = [0 < t_i < C]:  I_c = sum_i m_i x_ci [t_i = c],  S_c = sum_i m_i x_ci,  T_c = cnt[c] (one_hot(target * mask):
+// T_0 counts the unlabelled pixels),  D_c = S_c + T_c + 1e-6,  dice_c = (2 I_c + 1e-6) / D_c,  dc = mean_c dice_c,
+//   L = (-ln max(dc, 1e-6))^0.3,   dL/dx_ci = m_i K/C (2 [t_i = c] - dice_c) / D_c,   K = -0.3 (-ln dc)^-0.7 / dc  (0 for dc < 1e-6).
+// Every labelled pixel's gradient needs dice_c and D_c of all classes, so the class sums are a PRE-pass: the label histogram
+// stage also reads both probability maps at labelled pixels (loss_dice_sums_k, float64 partial sums per workgroup), one
+// small workgroup folds them in a fixed order (loss_dice_fold_k), and loss_pixel_k<true> adds the gradient in registers
+// -- no second pass over the gradient maps.  No floating-point atomics anywhere: bit-reproducible.
+#define DS_TILE 256
+#define DS_PER (DS_TILE / 64)
+static_assert(DS_PER % 4 == 0, "loss_dice_sums_k: wave w counts the labels of rounds k = w (mod 4) into the histogram");
+
+// one workgroup = DS_TILE consecutive pixels; every wave reads the tile's labels (DS_PER per lane) and owns the classes
+// c = wave, wave + 4, ...: per class the lanes sum their pixels in float64, a wave reduction gives the tile's S_c and I_c of
+// both heads -> parts[tile][head][2C] (S at c, I at C + c).  The label histogram (loss_count_k's) is built on the way.
+__global__ __launch_bounds__(256) void loss_dice_sums_k(const float* __restrict__ pl, const float* __restrict__ pc,
+                                                        const int64_t* __restrict__ label, int64_t HW, int64_t P, int C,
+                                                        unsigned long long* __restrict__ cnt, double* __restrict__ parts) {
+  __shared__ unsigned int h[LP_MAXC];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (threadIdx.x < LP_MAXC) h[threadIdx.x] = 0u;
+  __syncthreads();
+  const int64_t base = (int64_t)blockIdx.x * DS_TILE;
+  int t[DS_PER];
+  int64_t off[DS_PER];
+#pragma unroll
+  for (int k = 0; k < DS_PER; ++k) {
+    const int64_t i = base + k * 64 + lane;
+    t[k] = 0; off[k] = 0;
+    if (i < P) {
+      const int tt = (int)label[i];
+      if ((k & 3) == wave && tt >= 0 && tt < C) atomicAdd(&h[tt], 1u);       // (each pixel counted by one wave)
+      if (tt > 0 && tt < C) {
+        const int64_t n = i / HW;
+        t[k] = tt; off[k] = n * C * HW + (i - n * HW);
+      }
+    }
+  }
+  double* out = parts + (size_t)blockIdx.x * 4 * C;
+  for (int c = wave; c < C; c += 4) {
+    double sl = 0.0, il = 0.0, sc = 0.0, ic = 0.0;
+#pragma unroll
+    for (int k = 0; k < DS_PER; ++k) {
+      if (t[k] > 0) {
+        const double x = (double)pl[off[k] + c * HW], y = (double)pc[off[k] + c * HW];
+        sl += x; sc += y;
+        if (t[k] == c) { il += x; ic += y; }
+      }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+      sl += __shfl_down(sl, o); il += __shfl_down(il, o); sc += __shfl_down(sc, o); ic += __shfl_down(ic, o);
+    }
+    if (lane == 0) { out[c] = sl; out[C + c] = il; out[2 * C + c] = sc; out[3 * C + c] = ic; }
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < C && h[threadIdx.x]) atomicAdd(&cnt[threadIdx.x], (unsigned long long)h[threadIdx.x]);
+}
+
+// single workgroup, fixed summation order: parts[nparts][4C] -> dice[2][2 + 2C] = per head {L, K/C, dice_c[C], 1/D_c[C]}
+// (DF_GROUPS waves take every DF_GROUPS-th tile each, eight independent loads per trip; the group sums are added in group order)
+#define DF_GROUPS 16
+__global__ __launch_bounds__(64 * DF_GROUPS) void loss_dice_fold_k(const double* __restrict__ parts, int nparts, int C,
+                                                                   const unsigned long long* __restrict__ cnt,
+                                                                   double* __restrict__ dice) {
+  __shared__ double sh[DF_GROUPS][4 * LP_MAXC];
+  __shared__ double tot[4 * LP_MAXC];
+  __shared__ double dsh[2][LP_MAXC];
+  const int W = 4 * C, g = threadIdx.x >> 6;
+  for (int col = threadIdx.x & 63; col < W; col += 64) {
+    double a = 0.0;
+    for (int b0 = g; b0 < nparts; b0 += 8 * DF_GROUPS) {
+      double v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int b = b0 + u * DF_GROUPS;
+        v[u] = b < nparts ? parts[(size_t)b * W + col] : 0.0;
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) a += v[u];
+    }
+    sh[g][col] = a;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < W) {
+    double a = 0.0;
+    for (int k = 0; k < DF_GROUPS; ++k) a += sh[k][threadIdx.x];
+    tot[threadIdx.x] = a;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < 2 * C) {
+    const int head = threadIdx.x / C, c = threadIdx.x - head * C;
+    const double S = tot[head * 2 * C + c], I = tot[head * 2 * C + C + c];
+    const double D = S + (double)cnt[c] + 1e-6, dc = (2.0 * I + 1e-6) / D;
+    double* o = dice + head * (2 + 2 * C);
+    o[2 + c] = dc; o[2 + C + c] = 1.0 / D;
+    dsh[head][c] = dc;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    const int head = threadIdx.x;
+    double m = 0.0;
+    for (int c = 0; c < C; ++c) m += dsh[head][c];
+    m /= (double)C;
+    const double nl = -log(m > 1e-6 ? m : 1e-6);
+    double* o = dice + head * (2 + 2 * C);
+    o[0] = pow(nl, 0.3);
+    o[1] = m < 1e-6 ? 0.0 : -0.3 * pow(nl, -0.7) / m / (double)C;
+  }
+}
+
+// out10 = the Lovasz stage's out8 (slots 0..7 already written, total WITHOUT the Dice terms) + {dice, dice_cam} in slots
+// 8, 9 and added to the total
+__global__ void loss_dice_finish_k(const double* __restrict__ dice, int C, float* __restrict__ out) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    const double a = dice[0], b = dice[2 + 2 * C];
+    out[8] = (float)a; out[9] = (float)b;
+    out[0] = (float)((double)out[0] + a + b);
+  }
+}
+
+extern "C" int pmf_loss_dice_parts(int64_t P) { return (int)cdiv64(P, DS_TILE); }
+
+extern "C" int pmf_loss_pixel_dice(const float* lidar_prob, const float* camera_prob, const int64_t* label, const float* alpha,
+                                   int32_t N, int32_t C, int64_t HW, float focal_gamma, float tau, float gamma_per,
+                                   unsigned long long* cnt, float* grad_lidar, float* grad_camera, float* key, double* rows,
+                                   unsigned long long* conf_lidar, unsigned long long* conf_camera, double* parts,
+                                   double* dice, pmf_stream_t s) {
+  if (C < 2 || C > LP_MAXC || N < 1 || HW < 1) return PMF_E_ARG;
+  if (!lidar_prob || !camera_prob || !label || !alpha || !cnt || !grad_lidar || !grad_camera || !key || !rows || !parts ||
+      !dice || (conf_lidar == nullptr) != (conf_camera == nullptr))
+    return PMF_E_ARG;
+  const int64_t P = (int64_t)N * HW;
+  if (cdiv64(P, DS_TILE) > 0x7fffffffll) return PMF_E_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)s;
+  hipError_t e = hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * C, st);
+  if (e != hipSuccess) return (int)e;
+  const int nparts = (int)cdiv64(P, DS_TILE);
+  hipLaunchKernelGGL(loss_dice_sums_k, dim3((unsigned)nparts), dim3(256), 0, st, lidar_prob, camera_prob, label, HW, P, (int)C,
+                     cnt, parts);
+  hipLaunchKernelGGL(loss_dice_fold_k, dim3(1), dim3(64 * DF_GROUPS), 0, st, (const double*)parts, nparts, (int)C,
+                     (const unsigned long long*)cnt, dice);
+  LossPixelArgs a;
+  a.pl = lidar_prob; a.pc = camera_prob; a.label = label; a.alpha = alpha; a.cnt = cnt;
+  a.gl = grad_lidar; a.gc = grad_camera; a.key = key; a.rows = rows; a.conf_l = conf_lidar; a.conf_c = conf_camera;
+  a.HW = HW; a.P = P; a.C = C; a.fgamma = focal_gamma; a.tau = tau; a.gamma_per = gamma_per; a.w6 = nullptr; a.dice = dice;
+  hipLaunchKernelGGL(loss_pixel_k<true>, dim3((unsigned)cdiv64(P, LP_BLOCK)), dim3(LP_BLOCK), 0, st, a);
+  PMF_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int pmf_loss_dice_finish(const double* dice, int32_t C, float* out10, pmf_stream_t s) {
+  if (!dice || !out10 || C < 2 || C > LP_MAXC) return PMF_E_ARG;
+  hipLaunchKernelGGL(loss_dice_finish_k, dim3(1), dim3(64), 0, (hipStream_t)s, dice, (int)C, out10);
+  PMF_LAUNCH_CHECK();
+  return 0;
 }
 
 static int loss_lovasz_impl(const int64_t* perm, const float* key_sorted, const int64_t* label, int32_t N, int32_t C,

@@ -4,7 +4,7 @@
 // (torch/optim/adamw.py, torch/optim/sgd.py), evaluated in float32 per element.
 // A range launch is what lets the engine update the parameters whose gradients are final while the backward plan is still
 // running (engine.py _optimise_behind_events): an optimiser over the whole buffer has to wait for the last gradient.
-// HBM-bound: AdamW reads 16 B and writes 12 B per parameter, SGD reads 12 B and writes 8 B.
+// HBM-bound: AdamW reads 16 B and writes 12 B per parameter (20 B and 16 B with AMSGrad), SGD reads 12 B and writes 8 B.
 #include "common.h"
 #pragma clang fp contract(off)
 
@@ -38,6 +38,42 @@ __global__ __launch_bounds__(256) void adamw_range_k(float* __restrict__ p, cons
   } else {
     const int64_t j = n4 * 4 + (i - n4);       // the (n % 4) tail elements, one thread each
     if (j < n) upd(p[j], g[j], m[j], v[j]);
+  }
+}
+
+// AdamW with amsgrad=True (tasks/sensat_urban/pmf/trainer.py:83-84 of the reference): adamw_range_k's arithmetic with torch's
+// AMSGrad step (torch/optim/adam.py: torch.maximum(max_exp_avg_sqs, exp_avg_sq, out=max_exp_avg_sqs), then
+// denom = max_exp_avg_sq.sqrt() / bias_correction2_sqrt + eps).  20 B read and 16 B written per parameter.
+__global__ __launch_bounds__(256) void adamw_amsgrad_range_k(float* __restrict__ p, const float* __restrict__ g,
+                                                             float* __restrict__ m, float* __restrict__ v,
+                                                             float* __restrict__ vmax, int64_t n4, int64_t n, float lr,
+                                                             float beta1, float beta2, float eps, float keep, double beta1d,
+                                                             double beta2d, const float* __restrict__ step) {
+  const double st = (double)*step;
+  const float bc1 = (float)(1.0 - pow(beta1d, st)), bc2 = (float)(1.0 - pow(beta2d, st));
+  const float step_size = lr / bc1, bc2_sqrt = sqrtf(bc2), w1 = (float)(1.0 - beta1d), w2 = (float)(1.0 - beta2d);
+  const int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x;
+  auto upd = [&](float& pp, float gg, float& mm, float& vv, float& xx) {
+    pp = pp * keep;
+    mm = mm + w1 * (gg - mm);
+    vv = beta2 * vv + w2 * (gg * gg);
+    xx = (vv > xx || vv != vv) ? vv : xx;      // torch.maximum: a NaN in either operand stays (fmaxf would drop it)
+    const float denom = sqrtf(xx) / bc2_sqrt + eps;
+    pp -= step_size * (mm / denom);
+  };
+  if (i < n4) {
+    const f32x4 P = ((f32x4*)p)[i], M = ((f32x4*)m)[i], V = ((f32x4*)v)[i], X = ((f32x4*)vmax)[i], G = ((const f32x4*)g)[i];
+    float pa[4] = {P.x, P.y, P.z, P.w}, ma[4] = {M.x, M.y, M.z, M.w}, va[4] = {V.x, V.y, V.z, V.w}, xa[4] = {X.x, X.y, X.z, X.w};
+    const float ga[4] = {G.x, G.y, G.z, G.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) upd(pa[k], ga[k], ma[k], va[k], xa[k]);
+    ((f32x4*)p)[i] = f32x4{pa[0], pa[1], pa[2], pa[3]};
+    ((f32x4*)m)[i] = f32x4{ma[0], ma[1], ma[2], ma[3]};
+    ((f32x4*)v)[i] = f32x4{va[0], va[1], va[2], va[3]};
+    ((f32x4*)vmax)[i] = f32x4{xa[0], xa[1], xa[2], xa[3]};
+  } else {
+    const int64_t j = n4 * 4 + (i - n4);       // the (n % 4) tail elements, one thread each
+    if (j < n) upd(p[j], g[j], m[j], v[j], vmax[j]);
   }
 }
 
@@ -81,6 +117,21 @@ extern "C" int pmf_adamw_range(float* param, const float* grad, float* exp_avg, 
   hipLaunchKernelGGL(adamw_range_k, dim3((unsigned)cdiv64(threads, 256)), dim3(256), 0, (hipStream_t)s, param, grad, exp_avg,
                      exp_avg_sq, n4, n, (float)lr, (float)beta1, (float)beta2, (float)eps, (float)(1.0 - lr * weight_decay), beta1, beta2,
                      step);
+  PMF_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int pmf_adamw_amsgrad_range(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
+                                       float* max_exp_avg_sq, int64_t n, double lr, double beta1, double beta2, double eps,
+                                       double weight_decay, const float* step, pmf_stream_t s) {
+  if (n < 0 || !step || !max_exp_avg_sq) return PMF_E_ARG;
+  if (n == 0) return 0;
+  if (!param || !grad || !exp_avg || !exp_avg_sq) return PMF_E_ARG;
+  const int64_t n4 = (al16(param) && al16(grad) && al16(exp_avg) && al16(exp_avg_sq) && al16(max_exp_avg_sq)) ? n / 4 : 0;
+  const int64_t threads = n4 + (n - 4 * n4);
+  hipLaunchKernelGGL(adamw_amsgrad_range_k, dim3((unsigned)cdiv64(threads, 256)), dim3(256), 0, (hipStream_t)s, param, grad,
+                     exp_avg, exp_avg_sq, max_exp_avg_sq, n4, n, (float)lr, (float)beta1, (float)beta2, (float)eps,
+                     (float)(1.0 - lr * weight_decay), beta1, beta2, step);
   PMF_LAUNCH_CHECK();
   return 0;
 }

@@ -14,8 +14,8 @@ import os
 import torch
 import torch.nn as nn
 
-from .loss import (FocalSoftmaxLoss, Lovasz_softmax, MultiTaskLoss, pmf_total_loss, pmf_total_loss_fused,
-                   epmf_total_loss, weighted_loss_fused, EPMF_TERMS)
+from .loss import (FocalSoftmaxLoss, Lovasz_softmax, MultiTaskLoss, ExpLogDiceLoss, pmf_total_loss, pmf_total_loss_fused,
+                   epmf_total_loss, weighted_loss_fused, sensat_total_loss, sensat_total_loss_fused, EPMF_TERMS)
 from .metrics import IOUEval
 from .utils import WarmupCosineLR
 
@@ -30,6 +30,14 @@ def kitti_focal_alpha(cls_freq, learning_ignore):
     a = a / a.max()
     a[0] = 0
     return a.astype(np.float32), [c for c in range(len(w)) if w[c] < 1e-10]
+
+
+def sensat_focal_alpha(nclasses):
+    """tasks/sensat_urban/pmf/trainer.py:174-181: ones, 0 for the unlabelled class, larger weights for the rare classes."""
+    a = np.ones(nclasses, np.float32)
+    for c, v in ((0, 0.0), (4, 2.0), (5, 2.5), (7, 3.0), (12, 10.0), (13, 2.5)):
+        a[c] = v
+    return a
 
 
 class FlatOptimizerView(object):
@@ -150,7 +158,8 @@ class FlatOptimizerView(object):
 class TrainEngine:
     def __init__(self, model, nclasses, lr=1e-3, momentum=0.9, weight_decay=1e-5, lambda_=1.0, gamma=0.5, tau=0.7,
                  alpha=None, ignore_class=(0,), warmup_steps=1, max_steps=1, feature_mean=None, feature_std=None,
-                 distributed=False, device_ids=None, flat_state=True, adam_weight_decay=None, extra_adam_params=None):
+                 distributed=False, device_ids=None, flat_state=True, adam_weight_decay=None, extra_adam_params=None,
+                 amsgrad=False):
         self.raw_model = model
         dev = next(model.parameters()).device
         self.device = dev
@@ -190,6 +199,8 @@ class TrainEngine:
         if extra_adam_params:                               # EPMF: the MultiTaskLoss sigmas (tasks/epmf/trainer.py:105-106)
             adam_groups.append({"params": list(extra_adam_params)})
         adam_kw = {} if adam_weight_decay is None else {"weight_decay": adam_weight_decay}
+        if amsgrad:                                         # tasks/sensat_urban/pmf/trainer.py:83-84
+            adam_kw["amsgrad"] = True
         self.optimizer = torch.optim.AdamW(adam_groups, lr=lr, **adam_kw, **fused)
         self.aux_optimizer = torch.optim.SGD(camera_groups, lr=lr, nesterov=True, momentum=momentum,
                                              weight_decay=weight_decay, **fused)
@@ -235,7 +246,7 @@ class TrainEngine:
             return
         for opt, gi, kind in group_opts:
             pg = opt.param_groups[gi]
-            if pg.get("maximize") or pg.get("amsgrad") or len(pg["params"]) != 1:
+            if pg.get("maximize") or (pg.get("amsgrad") and kind != "adamw") or len(pg["params"]) != 1:
                 return                       # not the configurations the reference builds: leave them to torch
         self._ro = list(group_opts)
         if not (self.distributed and os.environ.get("PMF_DP_MODE", "events") == "segments"):
@@ -256,6 +267,8 @@ class TrainEngine:
                     st["step"] = torch.zeros((), dtype=torch.float32, device=fp.device)
                     st["exp_avg"] = torch.zeros_like(fp, memory_format=torch.preserve_format)
                     st["exp_avg_sq"] = torch.zeros_like(fp, memory_format=torch.preserve_format)
+                if opt.param_groups[gi].get("amsgrad") and "max_exp_avg_sq" not in st:
+                    st["max_exp_avg_sq"] = torch.zeros_like(fp, memory_format=torch.preserve_format)
                 if not (torch.is_tensor(st["step"]) and st["step"].is_cuda and st["step"].dtype == torch.float32):
                     st["step"] = torch.as_tensor(float(st["step"]), dtype=torch.float32, device=fp.device)
                 st["step"] += 1
@@ -281,7 +294,12 @@ class TrainEngine:
         o, n = 4 * (a - lo), b - a
         pp, gp = self.flat.param.data_ptr() + 4 * a, self.flat.grad.data_ptr() + 4 * a
         sp = C.c_void_p(stream.cuda_stream)
-        if kind == "adamw":
+        if kind == "adamw" and pg.get("amsgrad"):
+            rc = L.lib().pmf_adamw_amsgrad_range(pp, gp, st["exp_avg"].data_ptr() + o, st["exp_avg_sq"].data_ptr() + o,
+                                                 st["max_exp_avg_sq"].data_ptr() + o, n, float(pg["lr"]),
+                                                 float(pg["betas"][0]), float(pg["betas"][1]), float(pg["eps"]),
+                                                 float(pg["weight_decay"]), st["step"].data_ptr(), sp)
+        elif kind == "adamw":
             rc = L.lib().pmf_adamw_range(pp, gp, st["exp_avg"].data_ptr() + o, st["exp_avg_sq"].data_ptr() + o, n,
                                          float(pg["lr"]), float(pg["betas"][0]), float(pg["betas"][1]), float(pg["eps"]),
                                          float(pg["weight_decay"]), st["step"].data_ptr(), sp)
@@ -525,7 +543,10 @@ class TrainEngine:
         self.model.train()
         self._buffers_dirty = True
         pcd, rgb = self.prepare(input_feature, input_mask)
-        label = input_label.long()
+        return self._train_iteration(pcd, rgb, input_label.long())
+
+    def _train_iteration(self, pcd, rgb, label):
+        """forward, objective, backward, both optimisers, both schedules, confusion matrices (what follows prepare())"""
         total, terms, lidar_pred, camera_pred, metrics_done = self.forward_loss(pcd, rgb, label)
         if self.flat is None:
             self.optimizer.zero_grad(set_to_none=True)
@@ -565,7 +586,9 @@ class TrainEngine:
         if self.distributed and getattr(self, "_buffers_dirty", True) and self.flat is not None:
             self.sync_buffers()
         pcd, rgb = self.prepare(input_feature, input_mask)
-        label = input_label.long()
+        return self._eval_iteration(pcd, rgb, input_label.long())
+
+    def _eval_iteration(self, pcd, rgb, label):
         total, terms, lidar_pred, camera_pred, metrics_done = self.forward_loss(pcd, rgb, label)
         if not metrics_done:
             self.metrics.addBatch(lidar_pred.argmax(dim=1), label)
@@ -632,6 +655,84 @@ class EPMFEngine(TrainEngine):
         if self.distributed and self.mt_loss.sigma.grad is not None:
             import torch.distributed as dist
             dist.all_reduce(self.mt_loss.sigma.grad)      # (1 / world rides on the upstream gradient already)
+
+
+class SensatEngine(TrainEngine):
+    """One optimisation step of SensatUrban training (tasks/sensat_urban/pmf/trainer.py:275-340 of the reference; :342-376
+    validation): the PMF step with
+      * all EIGHT feature channels normalised and multiplied by the mask, the mask being channel 4 of the feature map itself,
+        and label = (label + 1) * mask (:278-285),
+      * focal + exp-log Dice as the classification term of both heads (:205-216) -- on the GPU inside the fused objective
+        (loss/fused.py sensat_total_loss_fused),
+      * AdamW(amsgrad=True) over the LiDAR stream (:83-84), as range updates behind the backward plan like TrainEngine's,
+      * the SensatUrban focal weights (sensat_focal_alpha).
+    Data-parallel and flat-state machinery are TrainEngine's."""
+
+    def __init__(self, model, nclasses, alpha=None, amsgrad=True, **kw):
+        super().__init__(model, nclasses, alpha=sensat_focal_alpha(nclasses) if alpha is None else alpha, amsgrad=amsgrad,
+                         **kw)
+        self.dice = ExpLogDiceLoss()
+
+    def prepare(self, input_feature, input_label):
+        """trainer.py:278-285 -> (pcd [N,5,H,W], rgb [N,3,H,W], label [N,H,W] int64)."""
+        x = input_feature
+        mask = x[:, 4]
+        label = (input_label.long() + 1) * mask.long()
+        if self.mean is None:
+            x = x * mask.unsqueeze(1)
+        elif x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4 and x.shape[1] == 8:
+            import ctypes as C
+            from . import _lib as L
+            # the mask is a channel of the tensor that is normalised in place: the kernel gets a COPY taken before the
+            # launch (clone, not contiguous(): for N = 1 the channel slice is contiguous already and would stay a view)
+            m = mask.clone(memory_format=torch.contiguous_format)
+            hw = x.shape[2] * x.shape[3]
+            L.check(L.lib().pmf_normalise_inplace(x.data_ptr(), x.stride(0), m.data_ptr(), self.mean.data_ptr(),
+                                                  self.std.data_ptr(), x.shape[0], 8, hw,
+                                                  C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)),
+                    "pmf_normalise_inplace")
+        else:
+            x = (x - self.mean) / self.std * mask.unsqueeze(1)
+        return x[:, 0:5], x[:, 5:8], label
+
+    def forward_loss(self, pcd, rgb, label):
+        lidar_pred, camera_pred = self.model(pcd, rgb)
+        if lidar_pred.is_cuda:
+            for m in (self.metrics, self.metrics_img):
+                if m.conf_matrix.device != lidar_pred.device:
+                    m.conf_matrix = m.conf_matrix.to(lidar_pred.device)
+            total, terms = sensat_total_loss_fused(lidar_pred, camera_pred, label, self.focal.alpha, self.lambda_,
+                                                   self.gamma, self.tau, self.focal.gamma, self.metrics.conf_matrix,
+                                                   self.metrics_img.conf_matrix, grad_out=self._plan_grad_buffers())
+            self.metrics.external_update()
+            self.metrics_img.external_update()
+            return total, terms, lidar_pred, camera_pred, True
+        total, terms = sensat_total_loss(lidar_pred, camera_pred, label, self.focal, self.lovasz, self.dice,
+                                         self.lambda_, self.gamma, self.tau)
+        return total, terms, lidar_pred, camera_pred, False
+
+    @staticmethod
+    def meter_values(terms):
+        """the reference's meters from the objective's terms: its LossFocal / LossFocal_img are focal + Dice
+        (trainer.py:210-211); computed when somebody reads them, not inside the step"""
+        return {"LossFocal": terms["foc"] + terms["dice"], "LossLovasz": terms["lov"],
+                "LossFocal_img": terms["foc_cam"] + terms["dice_cam"], "LossLovasz_img": terms["lov_cam"],
+                "LossPerception": terms["per"]}
+
+    def train_step(self, input_feature, input_label):
+        """one full iteration; everything stays on the device (no .item())."""
+        self.model.train()
+        self._buffers_dirty = True
+        pcd, rgb, label = self.prepare(input_feature, input_label)
+        return self._train_iteration(pcd, rgb, label)
+
+    @torch.no_grad()
+    def eval_step(self, input_feature, input_label):
+        self.model.eval()
+        if self.distributed and getattr(self, "_buffers_dirty", True) and self.flat is not None:
+            self.sync_buffers()
+        pcd, rgb, label = self.prepare(input_feature, input_label)
+        return self._eval_iteration(pcd, rgb, label)
 
 
 class SalsaNextEngine:

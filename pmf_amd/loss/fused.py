@@ -146,6 +146,64 @@ class _FusedWeightedLoss(torch.autograd.Function):
         return gl * g_total, gc * g_total, None, None, terms * g_total, None, None, None, None, None
 
 
+class _FusedSensatLoss(torch.autograd.Function):
+    """_FusedPMFLoss plus the exp-log Dice term of both heads (tasks/sensat_urban/pmf/trainer.py:205-216): the class sums are
+    a pre-pass inside the label-histogram stage, the Dice gradient is added in registers by the per-pixel kernel
+    (pmf_loss_pixel_dice), the Lovasz stage is the PMF objective's; out10 = out8 + {dice, dice_cam}."""
+
+    @staticmethod
+    def forward(ctx, lidar_prob, camera_prob, label, alpha, lambda_, gamma_per, tau, focal_gamma, conf_l, conf_c, grad_out=None):
+        lib = L.lib()
+        if not (lidar_prob.is_cuda and camera_prob.is_cuda and label.is_cuda):
+            raise RuntimeError("pmf_amd fused loss: tensors must live on the GPU (no CPU fallback)")
+        pl, pc = lidar_prob.detach().contiguous().float(), camera_prob.detach().contiguous().float()
+        lab = label.contiguous().long()
+        n, c, h, w = pl.shape
+        hw, p = h * w, n * h * w
+        dev = pl.device
+        gl, gc = _grad_buffers(pl, pc, grad_out)
+        key = torch.empty((2 * c, p), dtype=torch.float32, device=dev)
+        rows = torch.empty((lib.pmf_loss_rows(p), 4), dtype=torch.float64, device=dev)
+        cnt = torch.empty(c, dtype=torch.int64, device=dev)
+        nb = lib.pmf_loss_chunks(p)
+        bsum = torch.empty((2 * c, nb), dtype=torch.float32, device=dev)
+        dots = torch.empty((2 * c, nb), dtype=torch.float64, device=dev)
+        parts = torch.empty((lib.pmf_loss_dice_parts(p), 4 * c), dtype=torch.float64, device=dev)
+        dice = torch.empty((2, 2 + 2 * c), dtype=torch.float64, device=dev)
+        out10 = torch.empty(10, dtype=torch.float32, device=dev)
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        a = alpha.to(dev, torch.float32).contiguous()
+        L.check(lib.pmf_loss_pixel_dice(pl.data_ptr(), pc.data_ptr(), lab.data_ptr(), a.data_ptr(), n, c, hw,
+                                        float(focal_gamma), float(tau), float(gamma_per), cnt.data_ptr(), gl.data_ptr(),
+                                        gc.data_ptr(), key.data_ptr(), rows.data_ptr(),
+                                        conf_l.data_ptr() if conf_l is not None else None,
+                                        conf_c.data_ptr() if conf_c is not None else None, parts.data_ptr(),
+                                        dice.data_ptr(), st), "pmf_loss_pixel_dice")
+        ws = _sort_workspace(lib, c, p, dev)
+        L.check(lib.pmf_loss_lovasz_sort(key.data_ptr(), lab.data_ptr(), n, c, hw, cnt.data_ptr(), float(lambda_),
+                                         float(gamma_per), ws.data_ptr(), bsum.data_ptr(), dots.data_ptr(),
+                                         rows.data_ptr(), gl.data_ptr(), gc.data_ptr(), out10.data_ptr(), st),
+                "pmf_loss_lovasz_sort")
+        L.check(lib.pmf_loss_dice_finish(dice.data_ptr(), c, out10.data_ptr(), st), "pmf_loss_dice_finish")
+        ctx.save_for_backward(gl, gc)
+        ctx.mark_non_differentiable(out10)
+        return out10[0].clone(), out10
+
+    @staticmethod
+    def backward(ctx, g_total, _g_terms):
+        return _FusedPMFLoss.backward(ctx, g_total, _g_terms)
+
+
+def sensat_total_loss_fused(lidar_prob, camera_prob, label, alpha, lambda_=1.0, gamma_=0.5, tau=0.7, focal_gamma=2.0,
+                            conf_lidar=None, conf_camera=None, grad_out=None):
+    """the SensatUrban objective (perception.py sensat_total_loss) as one autograd node on the GPU.
+    returns (total, {"foc","lov","foc_cam","lov_cam","per","dice","dice_cam"}); conf_* as in pmf_total_loss_fused."""
+    total, o = _FusedSensatLoss.apply(lidar_prob, camera_prob, label, alpha, lambda_, gamma_, tau, focal_gamma,
+                                      conf_lidar, conf_camera, grad_out)
+    t = {"foc": o[1], "lov": o[2], "foc_cam": o[3], "lov_cam": o[4], "per": o[5], "dice": o[8], "dice_cam": o[9]}
+    return total, t
+
+
 def weighted_loss_fused(lidar_prob, camera_prob, label, alpha, w6, tau=0.7, focal_gamma=2.0, conf_lidar=None,
                         conf_camera=None, grad_out=None):
     """total = w6 . (foc, lov, foc_cam, lov_cam, per_p, per_q); w6: device tensor [6] (may require grad).

@@ -39,6 +39,16 @@ def pmf_total_loss(lidar_prob, camera_prob, label, focal, lovasz, lambda_=1.0, g
     return total, t
 
 
+def sensat_total_loss(lidar_prob, camera_prob, label, focal, lovasz, dice, lambda_=1.0, gamma_=0.5, tau=0.7):
+    """the SensatUrban objective (tasks/sensat_urban/pmf/trainer.py:205-216, 296-318): pmf_total_loss plus
+    dice(prob, label, mask = label > 0) per head.  "foc" / "foc_cam" stay the pure focal values (the reference's LossFocal
+    meter shows foc + dice); returns (total, dict of terms + entropies)."""
+    total, t = pmf_total_loss(lidar_prob, camera_prob, label, focal, lovasz, lambda_, gamma_, tau)
+    mask = label.gt(0)
+    t["dice"], t["dice_cam"] = dice(lidar_prob, label, mask=mask), dice(camera_prob, label, mask=mask)
+    return total + t["dice"] + t["dice_cam"], t
+
+
 def epmf_total_loss(lidar_prob, camera_prob, label, focal, lovasz, mt_loss, tau=0.7):
     """the EPMF multi-task objective with torch ops (tasks/epmf/trainer.py:376-430, use_mtloss): the six terms
     [foc_img, lov_img, per_img, per, foc, lov] through MultiTaskLoss in THAT order (sigma index = list position).
