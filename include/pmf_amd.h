@@ -169,8 +169,7 @@ typedef struct {
   const float* dbias_rows; /* optional: partial column sums of dz [dbias_nrows][dbias_ld] (pmf_bn_bwd_apply / */
   int32_t dbias_nrows, dbias_ld; /* pmf_act_bwd output); stage 2 folds them: dbias_out[co] += sum_r rows[r][co] */
   float* dbias_out;
-  int32_t cfg;            /* 0 = built-in heuristics; else (autotuner) NT | kernel << 8: NT = 32-channel output tiles per
-                           * workgroup (1, 2, 4); kernel 1 = pipelined (needs NT 1 and its shape conditions), 2 = unit-dealing */
+  int32_t reserved0;      /* must be 0 (PMF_E_ARG otherwise); keeps the offsets of the fields around it */
   int32_t flags;          /* PMF_WGRAD_S3: run the pipelined kernel's products on the bf16 matrix pipe (operands split three
                            * ways, six products, fp32 accumulate -- fp32-class error, conv_wgrad.hip); ignored where the
                            * pipelined kernel's shape conditions do not hold */
@@ -782,14 +781,13 @@ int pmf_conv_wgrad_nsplit(const pmf_wgrad_desc_t* d);
 int pmf_conv_wgrad_variant(const pmf_wgrad_desc_t* d);
 #define PMF_WG_UNIT 0       /* conv_wgrad_k: fp32 MFMA, output tiles dealt to the waves */
 #define PMF_WG_PIPE 1       /* conv_wgrad_pipe_k: fp32 MFMA, software-pipelined */
-#define PMF_WG_STAGED 2     /* conv_wgrad_s3_k: split-bf16, two barriers per tile (PMF_WG_SWP=0) */
 #define PMF_WG_SWP 3        /* conv_wgrad_s3_swp_k: split-bf16, software-pipelined, the waves split the pixels */
-#define PMF_WG_W8 4         /* conv_wgrad_s3_w8_k: split-bf16, eight waves (PMF_WG_W8=1) */
 #define PMF_WG_NSPLIT 5     /* conv_wgrad_s3n_k: split-bf16, the waves own different output-channel tiles */
 #define PMF_WG_DIRECT 6     /* wgrad_1x1_k: one tap, operands straight from global memory, fp32 MFMA */
 #define PMF_WG_DIRECT_S3 7  /* wgrad_1x1_s3_k: the same, split-bf16 */
 #define PMF_WG_STREAM 8     /* wgrad_stream_k: one tap, few channels, full-resolution maps */
 #define PMF_WG_FEWC 9       /* wgrad_fewc_k: <= 4 input channels (the 7x7 RGB stem) */
+/* (2 and 4 belonged to two retired split-bf16 kernels and are not reused) */
 /* sizeof() of the structs above, for bindings to self-check: 0 src, 1 conv, 2 wgrad, 3 view, 4 small, 5 op, 6 pack job */
 int pmf_sizeof(int which);
 

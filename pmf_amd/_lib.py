@@ -15,7 +15,8 @@ SRC_RELU, SRC_BCAST = 1, 2
 EP_STAT_X_ONLY = 1
 WGRAD_S3 = 1
 # pmf_conv_wgrad_variant (PMF_WG_*)
-WG_UNIT, WG_PIPE, WG_STAGED, WG_SWP, WG_W8, WG_NSPLIT, WG_DIRECT, WG_DIRECT_S3, WG_STREAM, WG_FEWC = range(10)
+WG_UNIT, WG_PIPE, WG_SWP, WG_NSPLIT, WG_DIRECT, WG_DIRECT_S3, WG_STREAM, WG_FEWC = 0, 1, 3, 5, 6, 7, 8, 9
+WG_STAGED, WG_W8 = 2, 4    # retired with their kernels (docs/rounds/r15.md): never returned, kept so that code naming them imports
 PMF_E_ARG, PMF_E_UNSUPPORTED = -1, -2
 BEV_NONFINITE, BEV_RANGE, BEV_INTERNAL = 1, 2, 4   # pmf_bev_extent_t.flags (PMF_BEV_*)
 CFG_DIRECT_TAPS = 1 << 24      # pmf_conv_desc_t.cfg: direct multi-tap variant (PMF_CFG_DIRECT_TAPS)
@@ -69,7 +70,7 @@ class WgradDesc(C.Structure):
                 ("partial", C.c_void_p), ("nsplit", C.c_int32), ("dw_oihw", C.c_void_p),
                 ("Cin_real", C.c_int32), ("KHW", C.c_int32), ("accumulate", C.c_int32),
                 ("dbias_rows", C.c_void_p), ("dbias_nrows", C.c_int32), ("dbias_ld", C.c_int32),
-                ("dbias_out", C.c_void_p), ("cfg", C.c_int32), ("flags", C.c_int32)]
+                ("dbias_out", C.c_void_p), ("reserved0", C.c_int32), ("flags", C.c_int32)]
 
 
 class View(C.Structure):

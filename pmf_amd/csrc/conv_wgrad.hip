@@ -487,18 +487,12 @@ __device__ __forceinline__ void conv_wgrad_pipe_body(const pmf_wgrad_desc_t& d, 
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// The same pipelined kernel with the products on the bf16 matrix pipe (operands split three ways, six products per
-// fp32 product: see conv_fwd.hip PIPE 5 for the arithmetic).  K of v_mfma_f32_32x32x16_bf16 = 16 consecutive pixels of
-// one row; both operands are wanted pixel-major per channel while memory is channel-major per pixel:
-//   * input tile: split while it is written to LDS as [pixel][plane][32 ci] bf16 (192 B per pixel: four consecutive
-//     pixels land in four different 64-B bank quarters) and read with ds_read_b64_tr_b16, the hardware transpose read:
-//     a 16-lane group fetches a [4 pixels][16 channels] block and every lane receives the 4 pixels of ITS channel --
-//     two reads per plane make the 8-pixel A fragment of a tap (any tap offset: it only shifts the pixel index);
-//   * dz keeps its LDS-DMA path (raw fp32 [pixel][32 co]); the wave that owns a 16-pixel slab reads its B fragment as
-//     8 ds_read_b32 and splits it in registers -- once per slab, shared by all TB taps (54 MFMAs).
-// Wave w owns slab w of every half tile (4 slabs of 16 pixels), TB accumulators as before.
-// Phase tracing of conv_wgrad_s3_k (tools/trace_wgrad.py builds a private copy with -DPMF_WG_TRACE): thread 0 of every
-// workgroup stamps s_memtime at phase boundaries.  Compiled out of libpmf_amd.so.
+// The split-bf16 kernels: the pipelined kernel's products on the bf16 matrix pipe (operands split three ways, six
+// products per fp32 product: see conv_fwd.hip PIPE 5 for the arithmetic).  Two bodies follow: conv_wgrad_s3_swp_body (the
+// four waves split the pixels of one 32 ci x 32 co tile; it carries the description of the LDS layout) and
+// conv_wgrad_s3n_body (the waves own different output-channel tiles).
+// Phase tracing of both (tools/trace_wgrad.py builds a private copy with -DPMF_WG_TRACE): thread 0 of every workgroup
+// stamps s_memtime at phase boundaries.  Compiled out of libpmf_amd.so.
 #ifdef PMF_WG_TRACE
 __device__ unsigned long long* pmf_wg_trace_buf = nullptr;
 extern "C" int pmf_wg_trace_set(void* p) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(pmf_wg_trace_buf), &p, sizeof(p)); }
@@ -568,265 +562,22 @@ __device__ __forceinline__ float ws3_mul(float a, float b) {
   return r;
 }
 
-template <int TB, int XSL>
-__device__ __forceinline__ void conv_wgrad_s3_body(const pmf_wgrad_desc_t& d, const WgGeom& g, float* __restrict__ smem) {
-  constexpr int BN = 32;
-  constexpr int HPX = 64;
-  constexpr int ZPW = HPX * BN / 256 / 4;   // 2 DMA instructions per wave per half
-  constexpr int PPI = 256 / BN;
-  char* __restrict__ Xs = (char*)smem;
-  float* __restrict__ Z0 = smem + g.x_floats;
-  float* __restrict__ Z1 = Z0 + HPX * BN;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int li = lane & 31, lh = lane >> 5;
-  const int split = blockIdx.x, chunk = blockIdx.y;
-  const int co0 = (int)blockIdx.z * BN;
-  const int in_cols = g.in_cols;
-
-  int wtri_ = 0;
-  (void)wtri_;
-  WTR();
-  int si = 0, c0 = 0, k0 = 0;
-  {
-    int rem = chunk;
-    for (;;) {
-      const int nch = (d.src[si].C + WG_CI - 1) / WG_CI;     // (a 16-channel operand is one half-empty chunk)
-      if (rem < nch) { c0 = rem * WG_CI; k0 += c0; break; }
-      rem -= nch; k0 += d.src[si].C; ++si;
-    }
-  }
-  const int sld = d.src[si].ldc, sflags = d.src[si].flags;
-  const int sH = d.OH, sW = d.OW;
-  const bool aff = d.src[si].scale != nullptr;
-  const int q = tid & 7, cch = c0 + q * 4;
-  const int kc = min(WG_CI, d.src[si].C - c0);      // channels of this chunk that exist
-  const bool qok = q * 4 < kc;                      // this thread's four channels exist (else: zeros)
-  const int totalX = g.in_rows * in_cols * 8;
-  int rc[XSL];
-#pragma unroll
-  for (int j = 0; j < XSL; ++j) {
-    const int f = tid + 256 * j, pix = f >> 3;
-    const int r = pix / in_cols, c = pix - r * in_cols;
-    rc[j] = f < totalX ? (r << 8 | c) : -1;
-  }
-  int offZ[ZPW];
-#pragma unroll
-  for (int jj = 0; jj < ZPW; ++jj) {
-    const int p = (ZPW * wave + jj) * PPI + lane / (BN / 4);       // wave w DMAs the 16 pixels of ITS slab (it alone reads them)
-    offZ[jj] = ((p >> 5) * d.OW + (p & 31)) * d.dz_ldc + (lane % (BN / 4)) * 4;
-  }
-  int toff[TB];
-#pragma unroll
-  for (int j = 0; j < TB; ++j)
-    toff[j] = (((int)d.tdy[j] - g.dy_min) * in_cols + ((int)d.tdx[j] - g.dx_min)) * WS3_XPB;
-  // transpose-read addressing: lane p of a 16-lane group supplies [pixel p/4][channels 4 (p%4) ...]; groups 1 / 3 read
-  // channels 16-31, groups 2 / 3 pixels 8-11 (the k = 8..15 half of the MFMA operand)
-  const int trofs = (((lane >> 5) * 8 + ((lane & 15) >> 2)) * WS3_XPB) + ((((lane >> 4) & 1) * 16 + (lane & 3) * 4) * 2);
-
-  f32x16 acc[TB];
-#pragma unroll
-  for (int j = 0; j < TB; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-
-  const __amdgpu_buffer_rsrc_t xrs_on =
-      __builtin_amdgcn_make_buffer_rsrc((void*)d.src[si].x, 0, d.N * sH * sW * sld * 4, 0x00020000);
-  const __amdgpu_buffer_rsrc_t xrs_off = __builtin_amdgcn_make_buffer_rsrc((void*)d.src[si].x, 0, 0, 0x00020000);
-  f32x4 rX[XSL];
-  unsigned okX = 0u;
-  int ncur = 0;
-  const int tiles_per_n = g.tiles_x * g.tiles_y;
-  auto fetch = [&](int tile, bool on) {
-    const int n = tile / tiles_per_n, rem = tile - n * tiles_per_n;
-    const int ty = rem / g.tiles_x, tx = rem - ty * g.tiles_x;
-    const int by = ty * WG_ROWS + g.dy_min, bx = tx * 32 + g.dx_min;
-    const __amdgpu_buffer_rsrc_t rs = on ? xrs_on : xrs_off;
-    okX = 0u;
-#pragma unroll
-    for (int j = 0; j < XSL; ++j) {
-      const int iy = by + (rc[j] >> 8), ix = bx + (rc[j] & 255);
-      const bool ok = qok && rc[j] >= 0 && iy >= 0 && iy < sH && ix >= 0 && ix < sW;
-      const int gp = ok ? (n * sH + iy) * sW + ix : -1;
-      okX |= ok ? (1u << j) : 0u;
-      rX[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (gp * sld + cch) * 4, 0, 0));
-    }
-    ncur = n;
-  };
-  auto zsrc = [&](int tile, int half) -> const float* {
-    const int n = tile / tiles_per_n, rem = tile - n * tiles_per_n;
-    const int ty = rem / g.tiles_x, tx = rem - ty * g.tiles_x;
-    return d.dz + ((size_t)(n * d.OH + ty * WG_ROWS + 2 * half) * d.OW + tx * 32) * d.dz_ldc + co0;
-  };
-  auto dma = [&](const float* __restrict__ src, float* __restrict__ dst) {
-#pragma unroll
-    for (int jj = 0; jj < ZPW; ++jj)
-      __builtin_amdgcn_global_load_lds(src + offZ[jj], (lds_ptr_t)(dst + (ZPW * wave + jj) * 256), 16, 0, 0);
-  };
-  typedef __attribute__((address_space(3))) ws16x4* lds_tr_t;
-  auto afrag = [&](const char* __restrict__ base, wbf16x8 (&a)[3]) {   // 8-pixel A fragment of one tap, three planes
-#ifdef PMF_WG_NOTR       /* ablation build: no transposing LDS reads */
-#pragma unroll
-    for (int p = 0; p < 3; ++p) { wu32x4 t = {(unsigned)(size_t)base, (unsigned)p, 1u, 2u}; asm volatile("" : "+v"(t)); a[p] = __builtin_bit_cast(wbf16x8, t); }
-    return;
-#endif
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-      const ws16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_t)(base + p * 64));
-      const ws16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_t)(base + p * 64 + 4 * WS3_XPB));
-      a[p] = __builtin_bit_cast(wbf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-    }
-  };
-  // one half tile = 2 rows x 32 pixels = 4 slabs of 16 pixels; wave w owns slab w of both halves.
-  // prep: B fragment dz[pixel 8 lh + e][co li], e = 0..7, of the wave's slab, split in registers
-  const int rr = wave >> 1, xs = (wave & 1) * 16;
-  auto prep = [&](const float* __restrict__ Zh, wbf16x8 (&bf)[3]) {
-    const float* zp = Zh + (rr * 32 + xs + lh * 8) * BN + li;
-    float z[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) z[e] = zp[e * BN];
-    wu32x4 b0, b1, b2;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      unsigned p0, p1, p2;
-      ws3_split2(z[2 * e], z[2 * e + 1], p0, p1, p2);
-      b0[e] = p0; b1[e] = p1; b2[e] = p2;
-    }
-    bf[0] = __builtin_bit_cast(wbf16x8, b0); bf[1] = __builtin_bit_cast(wbf16x8, b1); bf[2] = __builtin_bit_cast(wbf16x8, b2);
-  };
-  // mma: TB taps x 6 MFMAs of half h.  Taps go in groups of G with their MFMAs interleaved product-major (six MFMAs in a
-  // row into ONE accumulator are a dependent chain); the next group's A fragments are read while this group multiplies.
-  auto mma = [&](int h, const wbf16x8 (&bf)[3]) {
-    const char* xb = Xs + ((2 * h + rr) * in_cols + xs) * WS3_XPB + trofs;
-    constexpr int G = TB % 3 == 0 ? 3 : (TB % 2 == 0 ? 2 : 1), NG = TB / G;
-    wbf16x8 a[2][G][3];
-#pragma unroll
-    for (int t = 0; t < G; ++t) afrag(xb + toff[t], a[0][t]);
-    constexpr int PA[6] = {0, 1, 2, 0, 1, 0}, PB[6] = {2, 1, 0, 1, 0, 0};   // smallest terms first
-#pragma unroll
-    for (int gq = 0; gq < NG; ++gq) {
-      const int cur = gq & 1, nxt = cur ^ 1;
-      if (gq + 1 < NG) {
-#pragma unroll
-        for (int t = 0; t < G; ++t) afrag(xb + toff[(gq + 1) * G + t], a[nxt][t]);
-      }
-#pragma unroll
-      for (int pr = 0; pr < 6; ++pr)
-#pragma unroll
-        for (int t = 0; t < G; ++t)
-#ifdef PMF_WG_NOMFMA     /* ablation build of tools/trace_wgrad.py: keep the LDS reads alive, no matrix work */
-          acc[gq * G + t][pr] += __builtin_bit_cast(float, __builtin_bit_cast(wu32x4, a[cur][t][PA[pr]])[pr & 3] ^ __builtin_bit_cast(wu32x4, bf[PB[pr]])[pr & 3]);
-#else
-          acc[gq * G + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[cur][t][PA[pr]], bf[PB[pr]], acc[gq * G + t], 0, 0, 0);
-#endif
-    }
-  };
-
-  // Vector-memory queue of a wave (operations complete in order) while it computes tile t:  [dz half 0 (t)] [dz half 1 (t)]
-  // [input tile (t+1)].  Every wave DMAs and reads only its own dz slab, so the dz buffers need no barrier: a wave waits for
-  // ITS DMA (vmcnt), copies the slab into registers (prep) and re-issues the DMA of the next tile into the same slab at once.
-  // Both B fragments are prepared up front and the 2 x 54 MFMAs run as one stream.  Two barriers per tile (input tile
-  // write-after-read / read-after-write).
-  int tile = split;
-  if (tile < g.total_tiles) {
-    fetch(tile, true);
-    dma(zsrc(tile, 0), Z0);
-    dma(zsrc(tile, 1), Z1);
-  }
-  WTR();
-  while (tile < g.total_tiles) {
-    __syncthreads();                       // X: everyone finished reading the previous input tile
-    WTR();
-    f32x4 sc4 = {1.f, 1.f, 1.f, 1.f}, sh4 = {0.f, 0.f, 0.f, 0.f}, cm4 = {1.f, 1.f, 1.f, 1.f};
-    if (aff && qok) { sc4 = *(const f32x4*)(d.src[si].scale + cch); sh4 = *(const f32x4*)(d.src[si].shift + cch); }
-    if (d.src[si].cmul && qok) cm4 = *(const f32x4*)(d.src[si].cmul + (size_t)ncur * d.src[si].cmul_ld + cch);
-#pragma unroll
-    for (int j = 0; j < XSL; ++j) {
-      if (rc[j] >= 0) {
-        f32x4 t = {0.f, 0.f, 0.f, 0.f};
-        if ((okX >> j) & 1u) {
-          t = rX[j];
-          if (aff) t = t * sc4 + sh4;
-          if (sflags & PMF_SRC_RELU) {
-            t.x = fmaxf(t.x, 0.f); t.y = fmaxf(t.y, 0.f); t.z = fmaxf(t.z, 0.f); t.w = fmaxf(t.w, 0.f);
-          }
-          t = t * cm4;
-        }
-        unsigned l0, l1, l2, h0, h1, h2;
-        ws3_split2(t.x, t.y, l0, l1, l2);
-        ws3_split2(t.z, t.w, h0, h1, h2);
-        char* o = Xs + ((tid + 256 * j) >> 3) * WS3_XPB + q * 8;
-        *(wu32x2*)(o) = wu32x2{l0, h0};
-        *(wu32x2*)(o + 64) = wu32x2{l1, h1};
-        *(wu32x2*)(o + 128) = wu32x2{l2, h2};
-      }
-    }
-    const int next = tile + d.nsplit;
-    const bool have = next < g.total_tiles;
-    const int nt = have ? next : tile;     // past the end: re-request the current tile (keeps the queue shape; never used)
-    WTR();
-    __syncthreads();                       // Y: input tile visible
-    WTR();
-    fetch(nt, have);
-    wbf16x8 bf0[3], bf1[3];
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(XSL + ZPW) : "memory");    // my dz slab of half 0 landed
-    prep(Z0, bf0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                  // slab read: the DMA below may overwrite it
-    dma(zsrc(nt, 0), Z0);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(XSL + ZPW) : "memory");    // ... of half 1
-    prep(Z1, bf1);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    dma(zsrc(nt, 1), Z1);
-    WTR();
-    mma(0, bf0);
-    mma(1, bf1);
-    WTR();
-    tile = next;
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  WTR();
-
-  // ---- sum the four pixel groups (fixed order) and write this workgroup's partial slab
-  {
-    float* red = smem;   // [4 waves][16][64]
-#pragma unroll
-    for (int j = 0; j < TB; ++j) {
-      __syncthreads();
-      if (wave > 0) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) red[(wave * 16 + r) * 64 + lane] = acc[j][r];
-      }
-      __syncthreads();
-      if (wave == 0) {
-#pragma unroll
-        for (int p = 1; p < 4; ++p)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[j][r] += red[((p) * 16 + r) * 64 + lane];
-      }
-    }
-  }
-  if (wave == 0) {
-    float* part = d.partial + (size_t)split * d.ntaps * g.Ktot * g.Cout32;
-    const int co = co0 + li;
-#pragma unroll
-    for (int j = 0; j < TB; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int ci = (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (ci < kc) part[((size_t)j * g.Ktot + k0 + ci) * g.Cout32 + co] = acc[j][r];
-      }
-  }
-  WTR();
-  WTR_END();
-}
-
-// ---- conv_wgrad_s3_body, software-pipelined inside the wave (SWP) ---------------------------------------------------
-// 144 accumulator registers leave room for ONE wave per SIMD, so nothing in conv_wgrad_s3_body overlaps: per tile the
-// split + store of the input tile (3.2k cycles), the B-fragment preparation (3.0k) and two barrier rendezvous sit in
-// front of 108 MFMAs (4.7k; the pipe needs 3.5k) -- 28 % MFMA-busy (profiles/r02_trace_wgrad.txt).  Here the input tile
+// ---- split-bf16, software-pipelined inside the wave (SWP): the four waves split the pixels of one tile -----------------
+// K of v_mfma_f32_32x32x16_bf16 = 16 consecutive pixels of one row; both operands are wanted pixel-major per channel
+// while memory is channel-major per pixel:
+//   * input tile: split while it is written to LDS as [pixel][plane][32 ci] bf16 (192 B per pixel: four consecutive
+//     pixels land in four different 64-B bank quarters) and read with ds_read_b64_tr_b16, the hardware transpose read:
+//     a 16-lane group fetches a [4 pixels][16 channels] block and every lane receives the 4 pixels of ITS channel --
+//     two reads per plane make the 8-pixel A fragment of a tap (any tap offset: it only shifts the pixel index);
+//   * dz arrives by LDS-DMA (raw fp32 [pixel][32 co]); the wave that owns a 16-pixel slab reads its B fragment as
+//     8 ds_read_b32 and splits it in registers -- once per slab, shared by all TB taps (54 MFMAs).
+// Wave w owns slab w of every half tile (4 slabs of 16 pixels) and carries TB accumulators: 144 accumulator registers at
+// nine taps leave room for ONE wave per SIMD, so whatever is to overlap has to overlap inside the wave.  The input tile
 // is double-buffered in LDS and tile t + 1 is split and stored WHILE tile t is multiplied: the vector-ALU work and the
-// ds_writes are placed slot by slot between the tap groups of mma(), where they issue in the shadow of the 8-pass
-// MFMAs (one wave per SIMD: a filler next to an MFMA costs its issue slot only).  One barrier per tile instead of two.
+// ds_writes are placed slot by slot between the tap groups of tile_mma(), where they issue in the shadow of the 8-pass
+// MFMAs (one wave per SIMD: a filler next to an MFMA costs its issue slot only).  One barrier per tile.  (The loop this
+// replaced did split, B-fragment preparation and MFMAs one after the other behind two barriers per tile: DESIGN.md,
+// "Weight gradient: tried, measured, retired".)
 //   vector-memory queue of a wave at the top of iteration t:  [dz half 0 (t)] [dz half 1 (t)] [input tile (t+1)]
 template <int TB, int XSL>
 __device__ __forceinline__ void conv_wgrad_s3_swp_body(const pmf_wgrad_desc_t& d, const WgGeom& g, float* __restrict__ smem) {
@@ -887,6 +638,8 @@ __device__ __forceinline__ void conv_wgrad_s3_swp_body(const pmf_wgrad_desc_t& d
 #pragma unroll
   for (int j = 0; j < TB; ++j)
     toff[j] = (((int)d.tdy[j] - g.dy_min) * in_cols + ((int)d.tdx[j] - g.dx_min)) * WS3_XPB;
+  // transpose-read addressing: lane p of a 16-lane group supplies [pixel p/4][channels 4 (p%4) ...]; groups 1 / 3 read
+  // channels 16-31, groups 2 / 3 pixels 8-11 (the k = 8..15 half of the MFMA operand)
   const int trofs = (((lane >> 5) * 8 + ((lane & 15) >> 2)) * WS3_XPB) + ((((lane >> 4) & 1) * 16 + (lane & 3) * 4) * 2);
 
   f32x16 acc[TB];
@@ -967,7 +720,9 @@ __device__ __forceinline__ void conv_wgrad_s3_swp_body(const pmf_wgrad_desc_t& d
     *(wu32x2*)(o + 128) = wu32x2{l2, h2};
   };
   // ---- one tile: the MFMAs of tile t (2 x NG tap groups) with the split + store of tile t + 1 between the groups (slot
-  // by slot, into the other input buffer).  Measured and not kept: also moving the loads of tile t + 2 and the B-fragment
+  // by slot, into the other input buffer).  Taps go in groups of G with their MFMAs interleaved product-major (six MFMAs
+  // in a row into ONE accumulator are a dependent chain); the next group's A fragments are read while this group
+  // multiplies.  Measured and not kept: also moving the loads of tile t + 2 and the B-fragment
   // preparation of tile t + 1 between the groups (128 vs 120 us on 64 -> 64 3x3 d2 at 64x2048) -- with ONE wave per
   // SIMD the loop is bound by the number of instructions the wave has to issue (~770 per tile at one issue slot every
   // four cycles plus dependent-issue latency: the same 5.4k / 6.8k cycles with the MFMAs compiled out), not by the pipe.
@@ -1521,307 +1276,6 @@ template <int TB, int XSL, int NCO, bool RAG = false>
 __global__ __launch_bounds__(256) void conv_wgrad_s3n_k(const pmf_wgrad_desc_t d, const WgGeom g) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   conv_wgrad_s3n_body<TB, XSL, NCO, RAG>(d, g, smem);
-}
-
-// ---- eight waves per workgroup (W8): two waves per SIMD ----------------------------------------------------------------
-// What bounds conv_wgrad_s3_swp_body is the instruction stream of the ONE wave a SIMD holds (144 accumulator registers
-// per wave): ~770 instructions per tile at one issue slot every four cycles plus dependent-issue latency -- the loop
-// takes the same time with the MFMAs compiled out.  Here the taps of a 16-pixel slab are dealt to TWO waves (taps
-// [0, TBW) and [TBW, TB): 80 accumulator registers each), 512 threads per workgroup, so that every SIMD holds two
-// waves whose instruction streams interleave and the per-thread share of the split halves.
-//   * input tile: double-buffered in LDS as in the SWP body, 512 threads x XSL slots (4 or 5);
-//   * dz: both halves of a tile are 16 DMA instructions of 1 KiB, two per wave, into a double-buffered slab pair
-//     (a slab is read by the two waves that own its pixels: the barrier at the top of an iteration publishes it);
-//   * one barrier per tile.
-template <int TB, int XSL>
-__device__ __forceinline__ void conv_wgrad_s3_w8_body(const pmf_wgrad_desc_t& d, const WgGeom& g, float* __restrict__ smem) {
-  constexpr int BN = 32;
-  constexpr int HPX = 64;
-  constexpr int TBW = (TB + 1) / 2;             // taps of the first wave of a pair; the second takes TB - TBW
-  constexpr int NT = 512;
-  char* __restrict__ Xs0 = (char*)smem;
-  char* __restrict__ Xs1 = Xs0 + g.x_floats * 4;
-  float* __restrict__ Zb0 = (float*)(Xs1 + g.x_floats * 4);      // [2 halves][64 pixels][32 co], three tiles in flight
-  float* __restrict__ Zb1 = Zb0 + 2 * HPX * BN;
-  float* __restrict__ Zb2 = Zb1 + 2 * HPX * BN;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int slab = wave & 3, tset = wave >> 2;
-  const int li = lane & 31, lh = lane >> 5;
-  const int split = blockIdx.x, chunk = blockIdx.y;
-  const int co0 = (int)blockIdx.z * BN;
-  const int in_cols = g.in_cols;
-  int wtri_ = 0;
-  (void)wtri_;
-  WTR();
-
-  int si = 0, c0 = 0, k0 = 0;
-  {
-    int rem = chunk;
-    for (;;) {
-      const int nch = (d.src[si].C + WG_CI - 1) / WG_CI;     // (a 16-channel operand is one half-empty chunk)
-      if (rem < nch) { c0 = rem * WG_CI; k0 += c0; break; }
-      rem -= nch; k0 += d.src[si].C; ++si;
-    }
-  }
-  const int sld = d.src[si].ldc, sflags = d.src[si].flags;
-  const int sH = d.OH, sW = d.OW;
-  const bool aff = d.src[si].scale != nullptr, has_cm = d.src[si].cmul != nullptr;
-  const int q = tid & 7, cch = c0 + q * 4;
-  const int kc = min(WG_CI, d.src[si].C - c0);      // channels of this chunk that exist
-  const bool qok = q * 4 < kc;                      // this thread's four channels exist (else: zeros)
-  const int totalX = g.in_rows * in_cols * 8;
-  int rc[XSL], so[XSL];
-#pragma unroll
-  for (int j = 0; j < XSL; ++j) {
-    const int f = tid + NT * j, pix = f >> 3;
-    const int r = pix / in_cols, c = pix - r * in_cols;
-    rc[j] = (f < totalX && qok) ? (r << 8 | c) : (0x7fff << 8);
-    so[j] = ((r * sW + c) * sld + cch) * 4;
-  }
-  // dz: chunk k (0..15) of a tile = 8 pixels x 32 channels (1 KiB); wave w DMAs chunks 2 w and 2 w + 1
-  int offZ[2];
-#pragma unroll
-  for (int jj = 0; jj < 2; ++jj) {
-    const int p = (2 * wave + jj) * 8 + lane / 8;            // pixel 0..127 of the tile: row p / 32, column p % 32
-    offZ[jj] = ((p >> 5) * d.OW + (p & 31)) * d.dz_ldc + (lane % 8) * 4;
-  }
-  // own taps
-  const int t0 = tset ? TBW : 0;
-  int toff[TBW];
-#pragma unroll
-  for (int j = 0; j < TBW; ++j) {
-    const int t = min(t0 + j, TB - 1);
-    toff[j] = (((int)d.tdy[t] - g.dy_min) * in_cols + ((int)d.tdx[t] - g.dx_min)) * WS3_XPB;
-  }
-  const int trofs = (((lane >> 5) * 8 + ((lane & 15) >> 2)) * WS3_XPB) + ((((lane >> 4) & 1) * 16 + (lane & 3) * 4) * 2);
-
-  f32x16 acc[TBW];
-#pragma unroll
-  for (int j = 0; j < TBW; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-
-  const __amdgpu_buffer_rsrc_t xrs_on =
-      __builtin_amdgcn_make_buffer_rsrc((void*)d.src[si].x, 0, d.N * sH * sW * sld * 4, 0x00020000);
-  const __amdgpu_buffer_rsrc_t xrs_off = __builtin_amdgcn_make_buffer_rsrc((void*)d.src[si].x, 0, 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t crs = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(has_cm ? d.src[si].cmul : d.src[si].x), 0, (has_cm && qok) ? d.N * d.src[si].cmul_ld * 4 : 0, 0x00020000);
-  f32x4 sc4 = {1.f, 1.f, 1.f, 1.f}, sh4 = {0.f, 0.f, 0.f, 0.f};
-  if (aff && qok) { sc4 = *(const f32x4*)(d.src[si].scale + cch); sh4 = *(const f32x4*)(d.src[si].shift + cch); }
-  f32x4 rX[XSL], rC;
-  unsigned okX = 0u;
-  const int tiles_per_n = g.tiles_x * g.tiles_y;
-  int f_by = 0, f_bx = 0, f_base = 0, f_n = 0, f_ty = 0, f_tx = 0;
-  bool f_on = false;
-  auto fetch_coords = [&](int tile, bool on) {
-    const int n = tile / tiles_per_n, rem = tile - n * tiles_per_n;
-    const int ty = rem / g.tiles_x, tx = rem - ty * g.tiles_x;
-    f_by = ty * WG_ROWS + g.dy_min; f_bx = tx * 32 + g.dx_min;
-    f_base = ((n * sH + f_by) * sW + f_bx) * sld * 4;
-    f_n = n; f_on = on; f_ty = ty; f_tx = tx;
-  };
-  auto fetch_slot = [&](int j) {
-    const unsigned iy = (unsigned)(f_by + (rc[j] >> 8)), ix = (unsigned)(f_bx + (rc[j] & 255));
-    const bool ok = iy < (unsigned)sH && ix < (unsigned)sW;
-    okX = (okX & ~(1u << j)) | (ok ? (1u << j) : 0u);
-    const unsigned off = ok ? (unsigned)(f_base + so[j]) : 0x80000000u;
-    rX[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(f_on ? xrs_on : xrs_off, off, 0, 0));
-    if (j == XSL - 1)
-      rC = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(crs, (f_n * d.src[si].cmul_ld + cch) * 4, 0, 0));
-  };
-  auto dma_z = [&](int n, int ty, int tx, float* __restrict__ Zb) {
-    const float* src = d.dz + ((size_t)(n * d.OH + ty * WG_ROWS) * d.OW + tx * 32) * d.dz_ldc + co0;
-#pragma unroll
-    for (int jj = 0; jj < 2; ++jj)
-      __builtin_amdgcn_global_load_lds(src + offZ[jj], (lds_ptr_t)(Zb + (2 * wave + jj) * 256), 16, 0, 0);
-  };
-  typedef __attribute__((address_space(3))) ws16x4* lds_tr_t;
-  auto afrag = [&](const char* __restrict__ base, wbf16x8 (&a)[3]) {   // 8-pixel A fragment of one tap, three planes
-#ifdef PMF_WG_NOTR       /* ablation build: no transposing LDS reads */
-#pragma unroll
-    for (int p = 0; p < 3; ++p) { wu32x4 t = {(unsigned)(size_t)base, (unsigned)p, 1u, 2u}; asm volatile("" : "+v"(t)); a[p] = __builtin_bit_cast(wbf16x8, t); }
-    return;
-#endif
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-      const ws16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_t)(base + p * 64));
-      const ws16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_t)(base + p * 64 + 4 * WS3_XPB));
-      a[p] = __builtin_bit_cast(wbf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-    }
-  };
-  // the slab's pixels: half h = tile rows 2 h, 2 h + 1; slab s = row s / 2 of the half, pixels 16 (s % 2) ..
-  const int rr = slab >> 1, xs = (slab & 1) * 16;
-  auto prep = [&](const float* __restrict__ Zh, wbf16x8 (&bf)[3]) {
-    const float* zp = Zh + (rr * 32 + xs + lh * 8) * BN + li;
-    float z[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) z[e] = zp[e * BN];
-    wu32x4 b0, b1, b2;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      unsigned p0, p1, p2;
-      ws3_split2(z[2 * e], z[2 * e + 1], p0, p1, p2);
-      b0[e] = p0; b1[e] = p1; b2[e] = p2;
-    }
-    bf[0] = __builtin_bit_cast(wbf16x8, b0); bf[1] = __builtin_bit_cast(wbf16x8, b1); bf[2] = __builtin_bit_cast(wbf16x8, b2);
-  };
-  const int trash = g.in_rows * in_cols;
-  f32x4 cmS = {1.f, 1.f, 1.f, 1.f};
-  const float lo = (sflags & PMF_SRC_RELU) ? 0.f : -__builtin_inff();
-  auto store_slot = [&](int j, char* __restrict__ Xd) {
-    const bool ok = (okX >> j) & 1u;
-    f32x4 t;
-    t.x = ws3_fma(rX[j].x, sc4.x, sh4.x); t.y = ws3_fma(rX[j].y, sc4.y, sh4.y);
-    t.z = ws3_fma(rX[j].z, sc4.z, sh4.z); t.w = ws3_fma(rX[j].w, sc4.w, sh4.w);
-    t.x = ws3_vmax(t.x, lo); t.y = ws3_vmax(t.y, lo); t.z = ws3_vmax(t.z, lo); t.w = ws3_vmax(t.w, lo);
-    const float m = ok ? 1.f : 0.f;
-    t.x = ws3_mul(t.x, ws3_mul(cmS.x, m)); t.y = ws3_mul(t.y, ws3_mul(cmS.y, m));
-    t.z = ws3_mul(t.z, ws3_mul(cmS.z, m)); t.w = ws3_mul(t.w, ws3_mul(cmS.w, m));
-    unsigned l0, l1, l2, h0, h1, h2;
-    ws3_split2_np(t.x, t.y, l0, l1, l2);
-    ws3_split2_np(t.z, t.w, h0, h1, h2);
-    const int pix = (tid + NT * j) < totalX ? ((tid + NT * j) >> 3) : trash;
-    char* o = Xd + pix * WS3_XPB + q * 8;
-    *(wu32x2*)(o) = wu32x2{l0, h0};
-    *(wu32x2*)(o + 64) = wu32x2{l1, h1};
-    *(wu32x2*)(o + 128) = wu32x2{l2, h2};
-  };
-  // one tile: 2 halves x TBW taps; the A fragments of the next (half, tap) are read while this one multiplies; the slots
-  // of the next tile's split follow the taps one by one.  The second wave of a pair has one tap less when TB is odd: its
-  // last tap position is skipped (wave-uniform branch).
-  constexpr int NGT = 2 * TBW;
-  const bool last_tap = (t0 + TBW - 1) < TB;
-  wbf16x8 bf0[3], bf1[3];          // B fragments of the tile being multiplied
-  // Between the taps of tile t: split + store of tile t + 1, the loads of tile t + 2 into the registers a slot has
-  // freed, and the B fragments of tile t + 1 from the dz slabs the barrier at the top of the iteration has published.
-  auto tile_mma = [&](const char* __restrict__ Xc, char* __restrict__ Xn, const float* __restrict__ Zp) {
-    constexpr int PA[6] = {0, 1, 2, 0, 1, 0}, PB[6] = {2, 1, 0, 1, 0, 0};   // smallest terms first
-    wbf16x8 a[2][3], bn0[3], bn1[3];
-    const char* xb0 = Xc + ((0 + rr) * in_cols + xs) * WS3_XPB + trofs;
-    const char* xb1 = Xc + ((2 + rr) * in_cols + xs) * WS3_XPB + trofs;
-    afrag(xb0 + toff[0], a[0]);
-#pragma unroll
-    for (int gt = 0; gt < NGT; ++gt) {
-      const int cur = gt & 1, nxt = cur ^ 1;
-      const int h = gt / TBW, k = gt % TBW;
-      if (gt + 1 < NGT) afrag(((gt + 1) / TBW ? xb1 : xb0) + toff[(gt + 1) % TBW], a[nxt]);
-      if (k < TBW - 1 || last_tap) {
-#pragma unroll
-        for (int pr = 0; pr < 6; ++pr)
-          acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[cur][PA[pr]], (h ? bf1 : bf0)[PB[pr]], acc[k], 0, 0, 0);
-      }
-#ifndef PMF_WG_NOSPLIT
-#pragma unroll
-      for (int j = gt * XSL / NGT; j < (gt + 1) * XSL / NGT; ++j) { store_slot(j, Xn); fetch_slot(j); }
-#endif
-      if (gt == NGT / 2 - 1) prep(Zp, bn0);
-      if (gt == NGT - 2) prep(Zp + HPX * BN, bn1);
-    }
-#pragma unroll
-    for (int p = 0; p < 3; ++p) { bf0[p] = bn0[p]; bf1[p] = bn1[p]; }
-  };
-
-  // Vector-memory queue of a wave, oldest first, at the top of iteration t: [input t+1 (XSL + 1)]; my share of dz(t+1)
-  // has landed (the barrier publishes it)
-  int tile = split;
-  int cur = 0;
-  float* Zq0 = Zb0;   // dz(t)   -- consumed (B fragments prepared during iteration t - 1)
-  float* Zq1 = Zb1;   // dz(t+1) -- read during iteration t
-  float* Zq2 = Zb2;   // dz(t+2) -- DMA'd during iteration t
-  if (tile < g.total_tiles) {
-    fetch_coords(tile, true);
-#pragma unroll
-    for (int j = 0; j < XSL; ++j) fetch_slot(j);
-    dma_z(f_n, f_ty, f_tx, Zq0);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2) : "memory");            // the first input tile landed
-    if (has_cm) cmS = rC;
-#pragma unroll
-    for (int j = 0; j < XSL; ++j) store_slot(j, Xs0);
-    const int n1 = tile + d.nsplit;
-    fetch_coords(n1 < g.total_tiles ? n1 : tile, n1 < g.total_tiles);
-#pragma unroll
-    for (int j = 0; j < XSL; ++j) fetch_slot(j);
-    dma_z(f_n, f_ty, f_tx, Zq1);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(XSL + 1 + 2) : "memory");  // my share of dz(t) landed
-    __syncthreads();
-    prep(Zq0, bf0);
-    prep(Zq0 + HPX * BN, bf1);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(XSL + 1) : "memory");      // ... of dz(t + 1); queue: [input t+1]
-  }
-  WTR();
-  while (tile < g.total_tiles) {
-    const int next = tile + d.nsplit;
-    const char* Xc = cur ? Xs1 : Xs0;
-    char* Xn = cur ? Xs0 : Xs1;
-    const int n2 = next + d.nsplit;
-    const bool have2 = n2 < g.total_tiles;
-    fetch_coords(have2 ? n2 : tile, have2);
-    __syncthreads();                       // input tile t and dz(t + 1) complete; everyone finished with tile t - 1
-    WTR();
-    dma_z(f_n, f_ty, f_tx, Zq2);           // dz(t + 2); queue: [input t+1][dz t+2 (2)]
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2) : "memory");            // input tile t + 1 landed in registers
-    cmS.x = has_cm ? rC.x : 1.f; cmS.y = has_cm ? rC.y : 1.f; cmS.z = has_cm ? rC.z : 1.f; cmS.w = has_cm ? rC.w : 1.f;
-    WTR();
-    tile_mma(Xc, Xn, Zq1);                 // queue afterwards: [dz t+2 (2)][input t+2]
-    WTR();
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(XSL + 1) : "memory");      // my share of dz(t + 2) landed (published by the next barrier)
-    WTR();
-    tile = next;
-    cur ^= 1;
-    float* zt = Zq0; Zq0 = Zq1; Zq1 = Zq2; Zq2 = zt;
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  WTR();
-
-  // ---- sum the four pixel groups (fixed order) and write this workgroup's partial slab: per tap set, slabs 1..3 hand
-  // their accumulators to slab 0 through LDS
-  {
-    float* red = smem + tset * (3 * 16 * 64);   // [3 slabs][16][64] per tap set
-#pragma unroll
-    for (int j = 0; j < TBW; ++j) {
-      __syncthreads();
-      if (slab > 0) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) red[((slab - 1) * 16 + r) * 64 + lane] = acc[j][r];
-      }
-      __syncthreads();
-      if (slab == 0) {
-#pragma unroll
-        for (int p = 0; p < 3; ++p)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[j][r] += red[(p * 16 + r) * 64 + lane];
-      }
-    }
-  }
-  if (slab == 0) {
-    float* part = d.partial + (size_t)split * d.ntaps * g.Ktot * g.Cout32;
-    const int co = co0 + li;
-#pragma unroll
-    for (int j = 0; j < TBW; ++j) {
-      if (t0 + j < TB) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int ci = (r & 3) + 8 * (r >> 2) + 4 * lh;
-          if (ci < kc) part[((size_t)(t0 + j) * g.Ktot + k0 + ci) * g.Cout32 + co] = acc[j][r];
-        }
-      }
-    }
-  }
-  WTR();
-  WTR_END();
-}
-
-template <int TB, int XSL>
-__global__ __launch_bounds__(512) void conv_wgrad_s3_w8_k(const pmf_wgrad_desc_t d, const WgGeom g) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  conv_wgrad_s3_w8_body<TB, XSL>(d, g, smem);
-}
-
-template <int TB, int XSL>
-__global__ __launch_bounds__(256) void conv_wgrad_s3_k(const pmf_wgrad_desc_t d, const WgGeom g) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  conv_wgrad_s3_body<TB, XSL>(d, g, smem);
 }
 
 template <int TB, int NT, int XSL>
@@ -2395,7 +1849,7 @@ static bool wg_direct_s3(const pmf_wgrad_desc_t* d) {
   // resBlock5.r5 768 -> 256 at 2 x 4 x 128 27 -> 13 -- but 256 -> 256 at 1024 pixels 10 -> 13: from 4096 pixels, or from 1024
   // with >= 512 input channels
   constexpr int min_pix = 0;
-  if (!(d->flags & PMF_WGRAD_S3) || ((d->cfg >> 8) & 0xff) == 2) return false;
+  if (!(d->flags & PMF_WGRAD_S3)) return false;
   if (d->ntaps != 1 || d->gather || (d->in_stride != 1 && d->in_stride != 2) || d->tdy[0] || d->tdx[0] || (d->Cout & 1) || (d->dz_ldc & 1)) return false;
   const int64_t npix = (int64_t)d->N * d->OH * d->OW;
   if (d->Cout < 64) return false;   // full 64 x 64 blocks only (measured: narrower layers are faster on the other kernels)
@@ -2417,7 +1871,6 @@ static bool wg_direct_s3(const pmf_wgrad_desc_t* d) {
 // conditions of the direct 1x1 kernel + its grid
 static bool wg_direct_1x1(const pmf_wgrad_desc_t* d) {
   if (wg_direct_s3(d)) return true;
-  if (((d->cfg >> 8) & 0xff) == 2) return false;
   if (d->ntaps != 1 || d->gather || d->in_stride != 1 || d->tdy[0] || d->tdx[0] || (d->Cout & 1) || (d->dz_ldc & 1)) return false;
   for (int i = 0; i < d->nsrc; ++i) {
     const pmf_src_t& s = d->src[i];
@@ -2591,14 +2044,13 @@ __global__ __launch_bounds__(256) void wgrad_reduce_multi_k(const pmf_wgrad_desc
 // time), the launch and pmf_conv_wgrad_variant all read the same WgPick.  (A split count computed for another kernel than the
 // one launched is a workspace of the wrong size: a silent out-of-bounds write.)
 enum WgFamily {          // = PMF_WG_* of include/pmf_amd.h
-  WG_UNIT = PMF_WG_UNIT, WG_PIPE = PMF_WG_PIPE, WG_STAGED = PMF_WG_STAGED, WG_SWP = PMF_WG_SWP, WG_W8 = PMF_WG_W8,
-  WG_NSPLIT = PMF_WG_NSPLIT, WG_DIRECT = PMF_WG_DIRECT, WG_DIRECT_S3 = PMF_WG_DIRECT_S3, WG_STREAM = PMF_WG_STREAM,
-  WG_FEWC = PMF_WG_FEWC
+  WG_UNIT = PMF_WG_UNIT, WG_PIPE = PMF_WG_PIPE, WG_SWP = PMF_WG_SWP, WG_NSPLIT = PMF_WG_NSPLIT, WG_DIRECT = PMF_WG_DIRECT,
+  WG_DIRECT_S3 = PMF_WG_DIRECT_S3, WG_STREAM = PMF_WG_STREAM, WG_FEWC = PMF_WG_FEWC
 };
 struct WgPick {
   int family;
   int TB, NT;            // tiled families: taps per workgroup, 32-channel output tiles per workgroup (unit-dealing: 1 / 2 / 4)
-  int XSL;               // 16-byte input-tile slots per thread (7 / 9; eight-wave: 4 / 5)
+  int XSL;               // 16-byte input-tile slots per thread (7 / 9)
   int NCO, RAG;          // N-split: output-channel tiles per workgroup, partial 4 x 32-pixel tiles; direct 1x1 fp32: NCO
   int KG;                // few-channel: row tiles of 32 (tap, channel) pairs
   int KT, NTL;           // streaming: 32-row / 32-column tiles
@@ -2665,16 +2117,15 @@ static bool wg_fewc(const pmf_wgrad_desc_t* d) {
 
 // output-channel tiles per workgroup of the N-split split-bf16 kernel (conv_wgrad_s3n_k): 4 / 2 / 1, or 0 = not this kernel.
 // mode = PMF_WG_S3N: 0 switches it off (A/B), 2 caps it at two tiles.
-static int wg_s3n_nco(const pmf_wgrad_desc_t* d, const WgGeom& g, int TB, int mode, bool older) {
+static int wg_s3n_nco(const pmf_wgrad_desc_t* d, const WgGeom& g, int TB, int mode) {
   // (operands of 8 channels too -- EPMF's 3x3 5 -> 32 first layer, padded to 8: a quarter-full chunk; the rows of the 32-row
   // tile beyond the operand's channels are staged as zeros and never written to the slab)
   if (mode <= 1 || TB <= 1 || !(d->flags & PMF_WGRAD_S3) || !wg_simple(d, g, TB, 32, 8, true)) return 0;
   if ((int64_t)d->N * d->OH * d->OW * d->dz_ldc * 4 >= (1ll << 31)) return 0;
-  if (older) return 0;                                 // the test switches for the older variants
-  if (d->Cout % 32) return mode == 3 ? 0 : 1;          // ragged last tile: one tile per workgroup
+  if (d->Cout % 32) return 1;                          // ragged last tile: one tile per workgroup
   if (mode >= 4 && d->Cout % 128 == 0) return 4;
   if (d->Cout % 64 == 0) return 2;
-  return mode == 3 ? 0 : 1;       // (3: 32-channel tiles on the round-3 software-pipelined kernel)
+  return 1;
 }
 
 static void wg_pick(const pmf_wgrad_desc_t* d, WgPick* p) {
@@ -2714,30 +2165,20 @@ static void wg_pick(const pmf_wgrad_desc_t* d, WgPick* p) {
   // Pipelined kernels (when their conditions hold): NT = 1 -- every wave carries all TB taps of one 32-channel tile, the
   // narrow tile keeps the split count (hence the partial-slab traffic) low and measured fastest at every resolution.
   // Unit-dealing kernel: 64 output channels per workgroup (2 waves/SIMD fit; 128 measured slower).
-  // The variant switches are read per call, not cached: the tests flip them inside one process (a replayed graph never
+  // The variant switch is read per call, not cached: the tests flip it inside one process (a replayed graph never
   // comes here).
   const char* e_n = getenv("PMF_WG_S3N");
-  const char* e_swp = getenv("PMF_WG_SWP");
-  const char* e_w8 = getenv("PMF_WG_W8");
-  const bool swp = !(e_swp && e_swp[0] == '0'), w8 = e_w8 && e_w8[0] == '1';
   const int TB = (d->gather || d->ntaps == 1) ? 1 : (d->ntaps <= 4 ? 4 : 9);
   WgGeom& g = p->g;
   wg_geometry(d, TB, 32, &g, &lds);
   const bool s3 = (d->flags & PMF_WGRAD_S3) != 0;
-  const int kern = (d->cfg >> 8) & 0xff;
   const bool simple = wg_simple(d, g, TB, 32, s3 ? 16 : WG_CI);
-  const int nco = wg_s3n_nco(d, g, TB, e_n ? atoi(e_n) : 4, w8 || !swp);      // (> 0: ragged tiles / last channel tile too)
+  const int nco = wg_s3n_nco(d, g, TB, e_n ? atoi(e_n) : 4);      // (> 0: ragged tiles / last channel tile too)
   // 1x1 convolutions with wide outputs are plain GEMMs: one MFMA per operand pair either way, so the wider tile of
   // the unit-dealing kernel (fewer re-reads of the input tile) wins there (measured 123 vs 164 us on 384 -> 128)
   const bool wide_1x1 = d->ntaps == 1 && d->Cout > 64;
   int NT;
-  if (d->cfg) {                        // caller-tuned
-    NT = d->cfg & 0xff;
-    if (NT != 1 && NT != 2 && NT != 4) NT = 1;
-    if (NT == 4 && TB != 1) NT = 2;                        // 128-wide tiles are only built for per-tap staging
-    while (NT > 1 && (NT - 1) * 32 >= d->Cout) NT >>= 1;
-    if (kern == 1 && simple) NT = 1;
-  } else if (!wide_1x1 && (simple || nco > 0)) NT = 1;
+  if (!wide_1x1 && (simple || nco > 0)) NT = 1;
   else NT = wide_1x1 ? 4 : (d->Cout > 32 ? 2 : 1);
   wg_geometry(d, TB, NT * 32, &g, &lds);
   p->family = WG_UNIT; p->TB = TB; p->NT = NT; p->lds = lds;
@@ -2750,20 +2191,12 @@ static void wg_pick(const pmf_wgrad_desc_t* d, WgPick* p) {
     if (nco) {
       p->family = WG_NSPLIT; p->NCO = nco; p->RAG = d->OH % WG_ROWS || d->OW % 32;
       p->lds = xdb * 4; p->gz = cdiv(d->Cout, 32 * nco);
-    } else if (swp && w8 && TB > 1) {
-      // eight waves (the taps of a slab on two waves, two waves per SIMD): 3-10 % faster launch by launch, but 110 KiB
-      // of LDS and 512 threads leave no room for the input-gradient launches the weight gradients run next to:
-      // 16.08 vs 15.97 ms per step -- off unless PMF_WG_W8=1
-      p->family = WG_W8; p->block = 512; p->XSL = slots <= 512 * 4 ? 4 : 5;
-      p->lds = (xdb + 3 * WG_ROWS * 32 * 32) * 4;
-    } else if (swp) {    // input tile double-buffered: tile t + 1 is split while tile t is multiplied
+    } else {             // input tile double-buffered: tile t + 1 is split while tile t is multiplied
       p->family = WG_SWP; p->lds = (xdb + WG_ROWS * 32 * 32) * 4;
-    } else {
-      p->family = WG_STAGED; p->lds = (g.x_floats + WG_ROWS * 32 * 32) * 4;
     }
-    if (p->family != WG_STAGED) g.x_floats += WS3_XPB / 4;
+    g.x_floats += WS3_XPB / 4;
     if (p->lds < 16 * 1024) p->lds = 16 * 1024;            // room for the pixel-group fold
-  } else if (NT == 1 && wg_simple(d, g, TB, 32) && kern != 2) {
+  } else if (NT == 1 && wg_simple(d, g, TB, 32)) {
     p->family = WG_PIPE;
     if (p->lds < 16 * 1024) p->lds = 16 * 1024;            // room for the pixel-group reduction
   }
@@ -2785,6 +2218,7 @@ extern "C" int pmf_conv_wgrad_variant(const pmf_wgrad_desc_t* d) {
 }
 
 extern "C" int pmf_conv_wgrad_nsplit(const pmf_wgrad_desc_t* d) {
+  if (d->reserved0) return PMF_E_ARG;
   WgPick p;
   wg_pick(d, &p);
   int ns = p.target / p.per_split;
@@ -2866,9 +2300,7 @@ static int wg_launch_tiled(const WgPick& p, const pmf_wgrad_desc_t* d, hipStream
       if constexpr (TB == 1) { if (p.NT == 4) WG_GO(conv_wgrad_k<1, 4>); }
       break;
     case WG_PIPE: if (p.XSL == 7) WG_GO(conv_wgrad_pipe_k<TB, 1, 7>); else WG_GO(conv_wgrad_pipe_k<TB, 1, 9>);
-    case WG_STAGED: WG_XSL(conv_wgrad_s3_k, 7, 9);
     case WG_SWP: WG_XSL(conv_wgrad_s3_swp_k, 7, 9);
-    case WG_W8: if constexpr (TB > 1) WG_XSL(conv_wgrad_s3_w8_k, 4, 5); break;
     case WG_NSPLIT:
       if constexpr (TB > 1) { if (p.NCO == 4) WG_S3N(4); else if (p.NCO == 2) WG_S3N(2); else WG_S3N(1); }
       break;
@@ -2916,6 +2348,7 @@ static int wgrad_phases(const pmf_wgrad_desc_t* d, pmf_stream_t st, int phase) {
     return PMF_E_ARG;
   for (int i = 0; i < d->nsrc; ++i)
     if (d->src[i].C % 8 || d->src[i].ldc % 4) return PMF_E_ARG;
+  if (d->reserved0) return PMF_E_ARG;
   WgPick p;
   wg_pick(d, &p);
   if (phase & 1) {

@@ -192,17 +192,15 @@ def test_conv_unit_splitk_two_launch_form(name, monkeypatch):
         _conv_case(next(c for c in CONVS if c[0] == name), 32 | (1 << 8) | (ks << 16))
 
 
-WGRAD_VARIANT_ENVS = {"staged": {"PMF_WG_SWP": "0"}, "eight_waves": {"PMF_WG_W8": "1"}, "swp_pixel_split": {"PMF_WG_S3N": "0"},
-                      "nsplit_two_tiles": {"PMF_WG_S3N": "2"}}
+WGRAD_VARIANT_ENVS = {"swp_pixel_split": {"PMF_WG_S3N": "0"}, "nsplit_two_tiles": {"PMF_WG_S3N": "2"}}
 
 
 @pytest.mark.parametrize("env", list(WGRAD_VARIANT_ENVS.values()), ids=list(WGRAD_VARIANT_ENVS))
 def test_conv_unit_wgrad_variants(env, monkeypatch):
-    """the split-bf16 weight-gradient kernel's other forms (conv_wgrad.hip): the two-barrier staged loop that the
-    software-pipelined form replaced (PMF_WG_SWP=0), the 512-thread form with the taps of a slab on two waves
-    (PMF_WG_W8=1), the software-pipelined form with the four waves splitting the PIXELS of one 32 x 32 tile (PMF_WG_S3N=0:
-    what layers with 32 output channels run, and the default of rounds 3-4 everywhere) and the N-split form capped at two
-    output-channel tiles per workgroup (PMF_WG_S3N=2); same cases, same float64 bars"""
+    """the split-bf16 weight-gradient kernel's other forms (conv_wgrad.hip): the software-pipelined form with the four
+    waves splitting the PIXELS of one 32 x 32 tile (PMF_WG_S3N=0: the default of rounds 3-4 everywhere; by default only
+    small 1x1 layers and a dz of 2 GiB or more still run it -- layers with 32 output channels run N-split with one tile)
+    and the N-split form capped at two output-channel tiles per workgroup (PMF_WG_S3N=2); same cases, same float64 bars"""
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     ran = 0

@@ -1,7 +1,7 @@
 """Which weight-gradient kernel a descriptor gets, and the split count / workspace / stage-2 plan that go with it, pinned on
 the host (no GPU): pmf_conv_wgrad_nsplit, pmf_conv_wgrad_workspace, pmf_conv_wgrad_reduce_plan and pmf_conv_wgrad_variant
 against tests/golden/wgrad_dispatch.json, for every CONVS entry of tests/test_gpu_ops.py and every shape of
-tools/bench_conv.py, with PMF_WGRAD_S3 set and clear, under the default environment and the four environments of
+tools/bench_conv.py, with PMF_WGRAD_S3 set and clear, under the default environment and the two environments of
 test_conv_unit_wgrad_variants.  A split count computed for another kernel than the one launched is a partial-slab workspace
 of the wrong size, i.e. an out-of-bounds write no GPU test is certain to see.
 
@@ -26,12 +26,11 @@ from tools.bench_conv import CASES, wgrad_desc  # noqa: E402
 
 GOLDEN = os.path.join(ROOT, "tests", "golden", "wgrad_dispatch.json")
 ENVS = dict({"default": {}}, **WGRAD_VARIANT_ENVS)
-SWITCHES = ("PMF_WG_S3N", "PMF_WG_SWP", "PMF_WG_W8", "PMF_WGRAD_WGS")
+SWITCHES = ("PMF_WG_S3N", "PMF_WGRAD_WGS")
 # kernel template -> code of pmf_conv_wgrad_variant (include/pmf_amd.h)
-KERNEL_VARIANT = {"conv_wgrad_k": L.WG_UNIT, "conv_wgrad_pipe_k": L.WG_PIPE, "conv_wgrad_s3_k": L.WG_STAGED,
-                  "conv_wgrad_s3_swp_k": L.WG_SWP, "conv_wgrad_s3_w8_k": L.WG_W8, "conv_wgrad_s3n_k": L.WG_NSPLIT,
-                  "wgrad_1x1_k": L.WG_DIRECT, "wgrad_1x1_s3_k": L.WG_DIRECT_S3, "wgrad_stream_k": L.WG_STREAM,
-                  "wgrad_fewc_k": L.WG_FEWC} if hasattr(L, "WG_UNIT") else {}
+KERNEL_VARIANT = {"conv_wgrad_k": L.WG_UNIT, "conv_wgrad_pipe_k": L.WG_PIPE, "conv_wgrad_s3_swp_k": L.WG_SWP,
+                  "conv_wgrad_s3n_k": L.WG_NSPLIT, "wgrad_1x1_k": L.WG_DIRECT, "wgrad_1x1_s3_k": L.WG_DIRECT_S3,
+                  "wgrad_stream_k": L.WG_STREAM, "wgrad_fewc_k": L.WG_FEWC} if hasattr(L, "WG_UNIT") else {}
 
 
 def _copy(d):
@@ -64,7 +63,7 @@ def _probe(d):
     """what Plan._wgrad asks pmf_conv_wgrad_nsplit with: the shape, no pointers, no operand flags, no dz pitch"""
     p = _copy(d)
     p.dz = p.partial = p.dw_oihw = p.dbias_rows = p.dbias_out = None
-    p.dz_ldc = p.accumulate = p.dbias_nrows = p.dbias_ld = p.cfg = 0
+    p.dz_ldc = p.accumulate = p.dbias_nrows = p.dbias_ld = p.reserved0 = 0
     for i in range(L.MAX_SRC):
         s = p.src[i]
         s.x = s.scale = s.shift = s.cmul = None

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Phase trace of one conv_wgrad_s3_k launch: builds a private copy of conv_wgrad.hip with -DPMF_WG_TRACE (thread 0 of
-every workgroup stamps s_memtime at phase boundaries: start, loop entry, then per tile X-barrier / input tile stored /
-Y-barrier / B fragments ready / MFMAs done, loop exit, end) and prints the median cycle count of every phase.
+"""Phase trace of one split-bf16 weight-gradient launch (conv_wgrad_s3n_k or conv_wgrad_s3_swp_k, whichever the library
+selects for the case): builds a private copy of conv_wgrad.hip with -DPMF_WG_TRACE (thread 0 of every workgroup stamps
+s_memtime at phase boundaries: start, loop entry, then per tile the phases listed in `per` below, loop exit, end) and
+prints the median cycle count of every phase.
 usage: python tools/trace_wgrad.py [case-substring] [nsplit]     (cases of tools/bench_conv.py)"""
 import ctypes as C, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -50,10 +51,8 @@ def main(filt, ns):
         names = ["prologue"]
         # stamps per tile of the body that ran (the library's own selection, same PMF_WG_* environment as the traced copy)
         variant = lib.pmf_conv_wgrad_variant(C.byref(wd))
-        per = {L.WG_STAGED: ["X barrier", "split+store X", "Y barrier", "fetch + dz wait + B prep", "108 MFMAs"],
-               L.WG_NSPLIT: ["barrier + loads landed", "MFMAs + split(t+1) + dz prep", "fetch(t+2)"],
-               L.WG_SWP: ["barrier", "dz wait + B prep", "108 MFMAs + split(t+1)", "fetch(t+2)"],
-               L.WG_W8: ["barrier", "dz DMA + input wait", "MFMAs + split(t+1) + fetch(t+2) + B prep(t+1)", "dz wait"]}.get(variant)
+        per = {L.WG_NSPLIT: ["barrier + loads landed", "MFMAs + split(t+1) + dz prep", "fetch(t+2)"],
+               L.WG_SWP: ["barrier", "dz wait + B prep", "108 MFMAs + split(t+1)", "fetch(t+2)"]}.get(variant)
         if per is None:
             print("== %s: variant %d is not a split-bf16 tiled kernel, no stamps" % (name, variant)); continue
         ntile = (cnt - 1 - 1 - 2) // len(per)
