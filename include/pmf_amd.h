@@ -477,7 +477,9 @@ int pmf_color_jitter(uint8_t* image, int32_t h, int32_t w, const int32_t* order4
 /* Lovasz-softmax Jaccard gradient (pc_processor/loss/lovasz_softmax.py:56-68) for C class rows at once.
  * fg_sorted f32[C][P]: 0/1 foreground indicator, each row ordered by DESCENDING error with ignored pixels last;
  * n_valid: device int64, number of non-ignored pixels; bsum: f32[C][ceil(P/4096)] scratch.
- * grad[c][i] = jaccard_i - jaccard_{i-1}, jaccard_i = 1 - (G - cumsum(fg)_i) / (G + cumsum(1-fg)_i); 0 for i >= n_valid. */
+ * grad[c][i] = jaccard_i - jaccard_{i-1}, jaccard_i = 1 - (G - cumsum(fg)_i) / (G + cumsum(1-fg)_i); 0 for i >= n_valid.
+ * Counts and ranks are kept in float32, exact up to 2^24: P > 2^24 returns PMF_E_UNSUPPORTED without a launch.  The same
+ * limit holds for N * HW in pmf_loss_lovasz(_w) and pmf_loss_lovasz_sort(_w) below. */
 int pmf_lovasz_grad(const float* fg_sorted, int32_t C, int64_t P, const int64_t* n_valid, float* bsum, float* grad,
                     pmf_stream_t s);
 
@@ -517,7 +519,12 @@ int pmf_loss_lovasz_w(const int64_t* perm, const float* key_sorted, const int64_
  * unsorted key matrix pmf_loss_pixel wrote and sorts every used row -- classes that occur in the batch, pixels with a label
  * (the count P - cnt[0] is read on the device) -- by four stable 8-bit counting passes over the 30 significant bits of the
  * errors; equal errors keep ascending pixel order.  workspace: pmf_loss_sort_workspace(C, P) bytes.  Same outputs as
- * pmf_loss_lovasz (the Lovasz value does not depend on the order of equal errors). */
+ * pmf_loss_lovasz (the Lovasz value does not depend on the order of equal errors).
+ * N * HW > 2^24 (or a null workspace) is refused before the first launch: PMF_E_UNSUPPORTED (PMF_E_ARG).
+ * What the workspace holds afterwards, as tests/test_gpu_lovasz.py reads it: with R = 2C and P = N * HW it starts with four
+ * blocks of R * P 32-bit words, rows r = head * C + class of P words each (the digit histograms follow).  Block 3 holds the
+ * sorted pixel indices (uint32) and block 0 the sorted errors (float), over the first P - cnt[0] ranks of every row whose
+ * class is not 0 and occurs in cnt; all other rows and ranks are unspecified. */
 int64_t pmf_loss_sort_workspace(int32_t C, int64_t P);
 int pmf_loss_lovasz_sort(const float* key, const int64_t* label, int32_t N, int32_t C, int64_t HW,
                          const unsigned long long* cnt, float lambda, float gamma_per, void* workspace, float* bsum,

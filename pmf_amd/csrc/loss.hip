@@ -9,6 +9,10 @@
 #define LV_BLOCK 256
 #define LV_PER_THREAD 16
 #define LV_CHUNK (LV_BLOCK * LV_PER_THREAD)
+// The Jaccard kernels keep the foreground count G, the running count and the rank in float32, which counts exactly only up
+// to 2^24 (run += 1.f stops there), and lovasz2_grad_k packs the pixel index into 31 bits: every entry point of the Lovasz
+// stage refuses more pixels per row than this before its first launch.
+#define LV_MAXP ((int64_t)1 << 24)
 
 // (chunk b, row r) of a row-wise kernel.  2-D launch: (blockIdx.x, blockIdx.y).  1-D launch of 8 * ceil(R / 8) * nb
 // workgroups (rows_grid()): consecutive workgroup ids go round-robin over the 8 XCDs, so workgroup L runs on XCD L % 8 and
@@ -101,6 +105,7 @@ __global__ __launch_bounds__(LV_BLOCK) void lovasz_grad_k(const float* __restric
 extern "C" int pmf_lovasz_grad(const float* fg_sorted, int32_t C, int64_t P, const int64_t* n_valid, float* bsum,
                                float* grad, pmf_stream_t s) {
   if (C < 1 || P < 1) return PMF_E_ARG;
+  if (P > LV_MAXP) return PMF_E_UNSUPPORTED;
   const int nb = (int)cdiv64(P, LV_CHUNK);
   hipLaunchKernelGGL(lovasz_sums_k, dim3(nb, C), dim3(LV_BLOCK), 0, (hipStream_t)s, fg_sorted, P, nb, bsum);
   hipLaunchKernelGGL(lovasz_grad_k, dim3(nb, C), dim3(LV_BLOCK), 0, (hipStream_t)s, fg_sorted, P, nb,
@@ -671,6 +676,7 @@ static int loss_lovasz_impl(const int64_t* perm, const float* key_sorted, const 
                             float* bsum, double* dots, const double* rows, float* grad_lidar, float* grad_camera,
                             float* out6, pmf_stream_t s) {
   if (C < 2 || C > LP_MAXC || N < 1 || HW < 1) return PMF_E_ARG;
+  if (HW > LV_MAXP || (int64_t)N * HW > LV_MAXP) return PMF_E_UNSUPPORTED;
   const int64_t P = (int64_t)N * HW;
   const int nb = (int)cdiv64(P, LV_CHUNK);
   hipStream_t st = (hipStream_t)s;
@@ -885,8 +891,8 @@ static int loss_lovasz_sort_impl(const float* key, const int64_t* label, int32_t
                                  float* bsum, double* dots, const double* rows, float* grad_lidar, float* grad_camera,
                                  float* out8, pmf_stream_t s) {
   if (C < 2 || C > LP_MAXC || N < 1 || HW < 1 || !ws) return PMF_E_ARG;
+  if (HW > LV_MAXP || (int64_t)N * HW > LV_MAXP) return PMF_E_UNSUPPORTED;
   const int64_t P = (int64_t)N * HW;
-  if (P >= (1ll << 31)) return PMF_E_UNSUPPORTED;
   const int nb = (int)cdiv64(P, RS_CHUNK), R = 2 * C;
   hipStream_t st = (hipStream_t)s;
   unsigned* kA = (unsigned*)ws;

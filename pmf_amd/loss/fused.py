@@ -15,6 +15,12 @@ from .. import _lib as L
 
 
 _SORT_WS = {}
+MAX_PIXELS = 1 << 24       # the Lovasz stage counts ranks in float32 (include/pmf_amd.h): more pixels are PMF_E_UNSUPPORTED
+
+
+def _check_lovasz(rc, what, p):
+    if rc != 0:
+        L.check(rc, "%s on N*H*W = %d pixels (the Lovasz stage takes at most 2^24 = %d)" % (what, p, MAX_PIXELS))
 
 
 def _sort_workspace(lib, c, p, dev):
@@ -72,15 +78,15 @@ class _FusedPMFLoss(torch.autograd.Function):
                                    conf_c.data_ptr() if conf_c is not None else None, st), "pmf_loss_pixel")
         if _use_torch_sort():
             vals, perm = torch.sort(key, dim=1, descending=True)
-            L.check(lib.pmf_loss_lovasz(perm.data_ptr(), vals.data_ptr(), lab.data_ptr(), n, c, hw, cnt.data_ptr(),
-                                        float(lambda_), float(gamma_per), bsum.data_ptr(), dots.data_ptr(), rows.data_ptr(),
-                                        gl.data_ptr(), gc.data_ptr(), out6.data_ptr(), st), "pmf_loss_lovasz")
+            _check_lovasz(lib.pmf_loss_lovasz(perm.data_ptr(), vals.data_ptr(), lab.data_ptr(), n, c, hw, cnt.data_ptr(),
+                                              float(lambda_), float(gamma_per), bsum.data_ptr(), dots.data_ptr(), rows.data_ptr(),
+                                              gl.data_ptr(), gc.data_ptr(), out6.data_ptr(), st), "pmf_loss_lovasz", p)
         else:       # labelled pixels of the classes present only, sorted in the library (no torch.sort, no int64 indices)
             ws = _sort_workspace(lib, c, p, dev)
-            L.check(lib.pmf_loss_lovasz_sort(key.data_ptr(), lab.data_ptr(), n, c, hw, cnt.data_ptr(), float(lambda_),
-                                             float(gamma_per), ws.data_ptr(), bsum.data_ptr(), dots.data_ptr(),
-                                             rows.data_ptr(), gl.data_ptr(), gc.data_ptr(), out6.data_ptr(), st),
-                    "pmf_loss_lovasz_sort")
+            _check_lovasz(lib.pmf_loss_lovasz_sort(key.data_ptr(), lab.data_ptr(), n, c, hw, cnt.data_ptr(), float(lambda_),
+                                                   float(gamma_per), ws.data_ptr(), bsum.data_ptr(), dots.data_ptr(),
+                                                   rows.data_ptr(), gl.data_ptr(), gc.data_ptr(), out6.data_ptr(), st),
+                          "pmf_loss_lovasz_sort", p)
         ctx.save_for_backward(gl, gc)
         ctx.mark_non_differentiable(out6)
         return out6[0].clone(), out6
@@ -125,14 +131,14 @@ class _FusedWeightedLoss(torch.autograd.Function):
                                      conf_c.data_ptr() if conf_c is not None else None, st), "pmf_loss_pixel_w")
         if _use_torch_sort():
             vals, perm = torch.sort(key, dim=1, descending=True)
-            L.check(lib.pmf_loss_lovasz_w(perm.data_ptr(), vals.data_ptr(), lab.data_ptr(), n, c, hw, cnt.data_ptr(),
-                                          w.data_ptr(), bsum.data_ptr(), dots.data_ptr(), rows.data_ptr(), gl.data_ptr(),
-                                          gc.data_ptr(), out8.data_ptr(), st), "pmf_loss_lovasz_w")
+            _check_lovasz(lib.pmf_loss_lovasz_w(perm.data_ptr(), vals.data_ptr(), lab.data_ptr(), n, c, hw, cnt.data_ptr(),
+                                                w.data_ptr(), bsum.data_ptr(), dots.data_ptr(), rows.data_ptr(), gl.data_ptr(),
+                                                gc.data_ptr(), out8.data_ptr(), st), "pmf_loss_lovasz_w", p)
         else:
             ws = _sort_workspace(lib, c, p, dev)
-            L.check(lib.pmf_loss_lovasz_sort_w(key.data_ptr(), lab.data_ptr(), n, c, hw, cnt.data_ptr(), w.data_ptr(),
-                                               ws.data_ptr(), bsum.data_ptr(), dots.data_ptr(), rows.data_ptr(),
-                                               gl.data_ptr(), gc.data_ptr(), out8.data_ptr(), st), "pmf_loss_lovasz_sort_w")
+            _check_lovasz(lib.pmf_loss_lovasz_sort_w(key.data_ptr(), lab.data_ptr(), n, c, hw, cnt.data_ptr(), w.data_ptr(),
+                                                     ws.data_ptr(), bsum.data_ptr(), dots.data_ptr(), rows.data_ptr(),
+                                                     gl.data_ptr(), gc.data_ptr(), out8.data_ptr(), st), "pmf_loss_lovasz_sort_w", p)
         terms = torch.stack([out8[1], out8[2], out8[3], out8[4], out8[6], out8[7]])
         ctx.save_for_backward(gl, gc, terms)
         ctx.mark_non_differentiable(out8)
@@ -180,10 +186,10 @@ class _FusedSensatLoss(torch.autograd.Function):
                                         conf_c.data_ptr() if conf_c is not None else None, parts.data_ptr(),
                                         dice.data_ptr(), st), "pmf_loss_pixel_dice")
         ws = _sort_workspace(lib, c, p, dev)
-        L.check(lib.pmf_loss_lovasz_sort(key.data_ptr(), lab.data_ptr(), n, c, hw, cnt.data_ptr(), float(lambda_),
-                                         float(gamma_per), ws.data_ptr(), bsum.data_ptr(), dots.data_ptr(),
-                                         rows.data_ptr(), gl.data_ptr(), gc.data_ptr(), out10.data_ptr(), st),
-                "pmf_loss_lovasz_sort")
+        _check_lovasz(lib.pmf_loss_lovasz_sort(key.data_ptr(), lab.data_ptr(), n, c, hw, cnt.data_ptr(), float(lambda_),
+                                               float(gamma_per), ws.data_ptr(), bsum.data_ptr(), dots.data_ptr(),
+                                               rows.data_ptr(), gl.data_ptr(), gc.data_ptr(), out10.data_ptr(), st),
+                      "pmf_loss_lovasz_sort", p)
         L.check(lib.pmf_loss_dice_finish(dice.data_ptr(), c, out10.data_ptr(), st), "pmf_loss_dice_finish")
         ctx.save_for_backward(gl, gc)
         ctx.mark_non_differentiable(out10)
