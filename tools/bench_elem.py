@@ -9,8 +9,6 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from pmf_amd import _lib as L
 lib = L.lib()
-lib.pmf_debug_col.restype = C.c_int
-lib.pmf_debug_col.argtypes = [C.c_int32, C.c_int32]
 P = lambda t: C.c_void_p(t.data_ptr())
 def timeit(fn, n=100):
     for _ in range(50): fn()

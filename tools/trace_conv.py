@@ -20,8 +20,7 @@ def build():
     return C.CDLL(so)
 
 def main(filt, with_stats):
-    tl = build()
-    tl.pmf_conv_fwd.argtypes = [C.c_void_p, C.c_void_p]
+    tl = L.bind(build())
     ws = torch.empty(32 << 20, dtype=torch.uint8, device="cuda")
     for name, N, H, W, ci, co, k, dil in CASES:
         if filt and filt not in name: continue

@@ -21,8 +21,7 @@ def build():
     return C.CDLL(so)
 
 def main(filt, ns):
-    tl = build()
-    tl.pmf_conv_wgrad.argtypes = [C.c_void_p, C.c_void_p]
+    tl = L.bind(build())
     lib = L.lib()
     for name, N, H, W, ci, co, k, dil in CASES:
         if filt and filt not in name: continue
