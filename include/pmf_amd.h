@@ -498,7 +498,19 @@ int pmf_lovasz_grad(const float* fg_sorted, int32_t C, int64_t P, const int64_t*
  *   trainer.py:247-250).  Deterministic (fixed summation order).
  * The *_w variants take the weights of the six terms from DEVICE memory, w6 = {foc, lov, foc_cam, lov_cam, per_p,
  * per_q}: total = sum_i w6[i] * term_i -- the EPMF multi-task objective (tasks/epmf/trainer.py:409-430 with
- * pc_processor/loss/multi_task_loss.py: w_i = 1 / (2 sigma_i^2)) without a host round trip for the learned sigmas. */
+ * pc_processor/loss/multi_task_loss.py: w_i = 1 / (2 sigma_i^2)) without a host round trip for the learned sigmas.
+ * pmf_loss_pixel(_w) use w6[0, 2, 4, 5] only; w6[1] and w6[3] belong to the Lovasz stage.
+ * Guards of pmf_loss_pixel, pmf_loss_pixel_w and pmf_loss_pixel_dice, before anything is launched or written: C outside
+ *   [2, 32], N < 1, HW < 1, a null pointer among the probabilities, label, alpha, cnt, the gradient maps, key, rows (w6;
+ *   parts, dice), or ONE of conf_lidar / conf_camera null without the other: PMF_E_ARG.  Both null: no confusion matrices.
+ *   More than 2^31 - 1 blocks of 256 pixels: PMF_E_UNSUPPORTED.
+ * Where the stage is not the torch modules (pinned by tests/test_gpu_loss_pixel.py):
+ *   - a batch without a labelled pixel: FocalSoftmaxLoss(..., mask) divides 0 by 0 and returns NaN; here foc = foc_cam = 0
+ *     and the gradients are finite (the perception-aware terms alone);
+ *   - a probability of exactly 0 under an open gate: autograd of xlogy(p, p) gives ln 0 + 1 = -inf; here ln max(p, 1e-38).
+ *   The clamps 1e-8 (entropy, KL) and 1e-6 (focal) are the float32 constants: a float32 p equal to 1e-8f is not clamped.
+ *   Labels outside [0, C) are outside the contract (the modules raise): cnt and the confusion matrices do not count them
+ *   and they get no focal and no Dice gradient, but they count as labelled in the focal denominator P - cnt[0]. */
 int pmf_loss_rows(int64_t P);
 int pmf_loss_chunks(int64_t P);
 int pmf_loss_pixel(const float* lidar_prob, const float* camera_prob, const int64_t* label, const float* alpha,

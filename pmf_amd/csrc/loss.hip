@@ -483,7 +483,11 @@ static int loss_pixel_impl(const float* lidar_prob, const float* camera_prob, co
                            const float* w6, unsigned long long* cnt, float* grad_lidar, float* grad_camera, float* key,
                            double* rows, unsigned long long* conf_lidar, unsigned long long* conf_camera, pmf_stream_t s) {
   if (C < 2 || C > LP_MAXC || N < 1 || HW < 1) return PMF_E_ARG;
+  if (!lidar_prob || !camera_prob || !label || !alpha || !cnt || !grad_lidar || !grad_camera || !key || !rows ||
+      (conf_lidar == nullptr) != (conf_camera == nullptr))      // (the kernel tests conf_lidar alone and writes both)
+    return PMF_E_ARG;
   const int64_t P = (int64_t)N * HW;
+  if (cdiv64(P, LP_BLOCK) > 0x7fffffffll) return PMF_E_UNSUPPORTED;
   hipStream_t st = (hipStream_t)s;
   hipError_t e = hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * C, st);
   if (e != hipSuccess) return (int)e;
