@@ -12,3 +12,4 @@ _sys.modules["pc_processor.dataset.preprocess.augmentor"] = dataset.preprocess.a
 _sys.modules["pc_processor.dataset.preprocess.projection"] = dataset.preprocess.projection
 _sys.modules["pc_processor.dataset.sensat_urban.sensat_urban"] = dataset.sensat_urban.sensat_urban
 _sys.modules["pc_processor.dataset.sensat_urban.prepare"] = dataset.sensat_urban.prepare
+_sys.modules["pc_processor.dataset.sensat_urban.sensat_loader"] = dataset.sensat_urban.sensat_loader

@@ -2,7 +2,8 @@
 
 The header is the only place a constant, a struct member or a signature is written: read_header() turns its text into the
 PMF_* integers, the ctypes structs and the argtypes / restype of every prototype.  The reader is strict -- a declaration it
-cannot classify raises PMFLibraryError naming it, it never skips or guesses.
+cannot classify raises PMFLibraryError naming it, it never skips or guesses.  include/pmf_amd_sensat.h (the SensatUrban
+training loader) is a second header read the same way on top of the first: EXPORTS_SENSAT, BevSample.
 
 The product path has NO fallback: if the header or the shared library is missing, or the library's struct layout
 disagrees with the header, importing a compute entry point raises.
@@ -15,6 +16,7 @@ import types
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpmf_amd.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "pmf_amd.h")
+SENSAT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "pmf_amd_sensat.h")
 
 
 class PMFLibraryError(RuntimeError):
@@ -123,12 +125,21 @@ class _Reader:
         self.protos[name] = (restype, [self.declarator(p, st, False)[1] for p in params])
 
 
-def read_header(text, struct_names=None):
+def read_header(text, struct_names=None, base=None):
     """Parse the text of a C header of pmf_amd.h's kind.  Returns a namespace with
     consts: {name: int} of the `#define NAME <integer expression>` lines and the enumerators,
     structs: {C name: ctypes class} of the `typedef struct { ... } name;` blocks (class name from struct_names),
-    protos: {function: (restype, [argtypes])} in declaration order."""
+    protos: {function: (restype, [argtypes])} in declaration order,
+    aliases: {name: (base type, stars)} of the `typedef T* name;` lines.
+    base: the namespace of a header this one includes (`#include` lines are skipped, not followed): its constants, structs
+    and aliases are known while reading, and only what THIS text declares is returned."""
     r, names = _Reader(), struct_names or {}
+    inherited = (set(), set())
+    if base is not None:
+        r.consts.update(base.consts)
+        r.structs.update(base.structs)
+        r.aliases.update(base.aliases)
+        inherited = (set(base.consts), set(base.structs))
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text.replace("\\\n", " "), flags=re.S)
     text = re.sub(r"#\s*ifdef\s+__cplusplus\b.*?#\s*endif", " ", text, flags=re.S)
     for line in re.findall(r"^[ \t]*#[^\n]*", text, re.M):
@@ -166,7 +177,9 @@ def read_header(text, struct_names=None):
             r.aliases[m.group(3)] = (base, m.group(2).count("*"))
             continue
         r.prototype(st)
-    return types.SimpleNamespace(consts=r.consts, structs=r.structs, protos=r.protos)
+    return types.SimpleNamespace(consts={k: v for k, v in r.consts.items() if k not in inherited[0]},
+                                 structs={k: v for k, v in r.structs.items() if k not in inherited[1]},
+                                 protos=r.protos, aliases=r.aliases)
 
 
 # header name -> name in this module
@@ -175,31 +188,40 @@ _STRUCT_NAMES = {"pmf_src_t": "Src", "pmf_conv_dst_t": "ConvDst", "pmf_conv_desc
                  "pmf_pack_job_t": "PackJob", "pmf_bev_extent_t": "BevExtent"}
 
 
-def _read():
-    if not os.path.exists(HEADER_PATH):
+_SENSAT_STRUCT_NAMES = {"pmf_bev_sample_t": "BevSample"}
+
+
+def _read(path=None, struct_names=_STRUCT_NAMES, base=None):
+    path = HEADER_PATH if path is None else path
+    if not os.path.exists(path):
         raise PMFLibraryError("pmf_amd: %s not found -- the binding is derived from the header, it ships with the package "
-                              "tree.  There is no hand-written copy to fall back to." % HEADER_PATH)
-    with open(HEADER_PATH) as f:
-        h = read_header(f.read(), _STRUCT_NAMES)
-    lacking = [c for c in _STRUCT_NAMES if c not in h.structs]
+                              "tree.  There is no hand-written copy to fall back to." % path)
+    with open(path) as f:
+        h = read_header(f.read(), struct_names, base)
+    lacking = [c for c in struct_names if c not in h.structs]
     if lacking:
-        raise PMFLibraryError("pmf_amd: %s does not define %s" % (HEADER_PATH, ", ".join(lacking)))
+        raise PMFLibraryError("pmf_amd: %s does not define %s" % (path, ", ".join(lacking)))
     return h
 
 
 _H = _read()
+# the SensatUrban training loader's part of the ABI (csrc/bev_train.hip): a header of its own on top of the first one
+_HS = _read(SENSAT_HEADER_PATH, _SENSAT_STRUCT_NAMES, _H)
 # PMF_ACT_RELU -> ACT_RELU, PMF_OP_CONV -> OP_CONV, PMF_MAX_SRC -> MAX_SRC ...; the error codes keep their prefix (PMF_E_ARG)
 globals().update((k if k.startswith("PMF_E_") else k[4:], v) for k, v in _H.consts.items() if k.startswith("PMF_"))
 globals().update((py, _H.structs[c]) for c, py in _STRUCT_NAMES.items())
 WG_STAGED, WG_W8 = 2, 4    # retired with their kernels (docs/rounds/r15.md): never returned, kept so that code naming them imports
 OP_NAMES = {v: k for k, v in list(globals().items()) if k.startswith("OP_")}
 EXPORTS = list(_H.protos)       # every function the header declares
+globals().update((k[4:], v) for k, v in _HS.consts.items() if k.startswith("PMF_"))      # BEV_HFLIP, BEV_VFLIP
+globals().update((py, _HS.structs[c]) for c, py in _SENSAT_STRUCT_NAMES.items())
+EXPORTS_SENSAT = list(_HS.protos)       # every function pmf_amd_sensat.h declares
 
 
 def bind(handle):
     """Set restype and argtypes of every function of the header that `handle` (a CDLL of this library, or of a private
     build of some of its sources) exports; returns the handle."""
-    for name, (restype, argtypes) in _H.protos.items():
+    for name, (restype, argtypes) in list(_H.protos.items()) + list(_HS.protos.items()):
         fn = getattr(handle, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes
@@ -222,10 +244,16 @@ def lib():
     missing = [name for name in EXPORTS if not hasattr(L, name)]
     if missing:
         raise PMFLibraryError("pmf_amd: %s lacks %s, which include/pmf_amd.h declares" % (LIB_PATH, ", ".join(missing)))
+    missing = [name for name in EXPORTS_SENSAT if not hasattr(L, name)]
+    if missing:
+        raise PMFLibraryError("pmf_amd: %s lacks %s, which include/pmf_amd_sensat.h declares" % (LIB_PATH, ", ".join(missing)))
     for which, st in enumerate((Src, ConvDesc, WgradDesc, View, SmallArgs, Op, PackJob)):    # the order pmf_sizeof documents
         if L.pmf_sizeof(which) != C.sizeof(st):
             raise PMFLibraryError("pmf_amd ABI mismatch for %s: lib %d vs binding %d"
                                   % (st.__name__, L.pmf_sizeof(which), C.sizeof(st)))
+    if L.pmf_sizeof_sensat() != C.sizeof(BevSample):
+        raise PMFLibraryError("pmf_amd ABI mismatch for BevSample: lib %d vs binding %d"
+                              % (L.pmf_sizeof_sensat(), C.sizeof(BevSample)))
     _lib = L
     return L
 

@@ -3,7 +3,7 @@
 (tasks/sensat_urban/pmf/config_server.yaml: batch 4, 320 x 320, 14 classes, base_channels 48, resnet101, its eight
 feature means and stds).
 
-    python tools/bench_sensat_train.py [--part all|objective|optim|step|step_torch_optim] [--rounds R] [--calls K]
+    python tools/bench_sensat_train.py [--part all|objective|optim|step|step_torch_optim|loader_step] [--rounds R] [--calls K]
 
   objective          the fused objective with the Dice term (sensat_total_loss_fused) against (i) the PMF objective without it
                      (pmf_total_loss_fused, whose kernels this extension leaves as they were) and (ii) sensat_total_loss in
@@ -12,8 +12,11 @@ feature means and stds).
                      AdamW(amsgrad=True).step() on a tensor of the same size, with the bytes each moves
   step               SensatEngine.train_step with the range optimiser
   step_torch_optim   the same with PMF_OWN_OPTIM=0 (torch's fused step() at the end of the iteration)
+  loader_step        SensatLoader.batch() (two synthetic 3000 x 4000 frames resident on the device, the draws, the count and
+                     the gather of csrc/bev_train.hip) feeding SensatEngine.train_step, against the step alone on the batch
+                     it returned; host clock around iterations that end in a device synchronise
 
-``--part all`` (default) runs the four parts one after the other, each as a child process under its own time limit, and
+``--part all`` (default) runs the five parts one after the other, each as a child process under its own time limit, and
 stops at the first one that fails.  Every figure is a median over rounds of device-event timings; the variants of a part
 alternate within a round and every round works on freshly allocated inputs.  One JSON line per figure."""
 import argparse
@@ -30,7 +33,7 @@ BASE, BACKBONE = 48, "resnet101"
 MEAN = [27.47, 26.90, 27.22, 0.63, 0.81, 0, 0, 0]
 STD = [18.43, 18.00, 18.21, 0.40, 0.39, 255.0, 255.0, 255.0]
 FILL = 0.5                                    # labelled fraction of the synthetic label maps
-LIMITS = {"objective": 300, "optim": 240, "step": 420, "step_torch_optim": 420}      # seconds per child
+LIMITS = {"objective": 300, "optim": 240, "step": 420, "step_torch_optim": 420, "loader_step": 420}      # seconds per child
 
 
 def _median(xs):
@@ -171,6 +174,79 @@ def part_step(rounds, calls, own):
           spread_ms=[min(times) / 1e3, max(times) / 1e3], last_total=total.item())
 
 
+def part_loader_step(rounds, calls):
+    os.environ["PMF_OWN_OPTIM"] = "1"
+    import random
+    import time
+    import numpy as np
+    import torch
+    from pmf_amd.dataset import SensatLoader
+    from pmf_amd.engine import SensatEngine
+    from pmf_amd.models import PMFNet
+    from pmf_amd.utils.detinit import deterministic_init
+    dev = "cuda"
+    fh, fw = 3000, 4000
+
+    class Frames(object):
+        split = "train"
+
+        def __init__(self, n):
+            g = torch.Generator().manual_seed(2)
+            mean, std = torch.tensor(MEAN).view(8, 1, 1).double(), torch.tensor(STD).view(8, 1, 1).double()
+            self.frames = []
+            for _ in range(n):
+                fm = mean + std * torch.randn(8, fh, fw, generator=g, dtype=torch.float64)
+                fm[4] = (torch.rand(fh, fw, generator=g) < FILL).double()
+                lm = torch.randint(-1, C - 1, (fh, fw), generator=g)
+                self.frames.append({"feature_map": fm.numpy(), "label_map": lm.numpy().astype(np.int64)})
+
+        def readDataByIndex(self, i):
+            return self.frames[i]
+
+        def __len__(self):
+            return len(self.frames)
+    torch.manual_seed(0)
+    random.seed(0)
+    ld = SensatLoader(Frames(2), img_h=H, img_w=W, n_samples_split=200, device=dev)
+    model = deterministic_init(PMFNet(5, 3, C, BASE, imagenet_pretrained=False, image_backbone=BACKBONE)).to(dev)
+    eng = SensatEngine(model, C, lr=1e-3, warmup_steps=10, max_steps=10 ** 6, feature_mean=MEAN, feature_std=STD)
+    order = torch.randperm(len(ld)).tolist()
+    pos = [0]
+
+    def indices():
+        idx = [order[(pos[0] + k) % len(order)] for k in range(N)]
+        pos[0] += N
+        return idx
+
+    def host_timed(fn, n):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / n * 1e3
+
+    feat, raw = ld.batch(indices())
+    variants = {"loader_and_step": lambda: eng.train_step(*ld.batch(indices())),
+                "step_alone": lambda: eng.train_step(feat.clone(), raw),
+                "loader_alone": lambda: ld.batch(indices())}
+    times = {k: [] for k in variants}
+    for r in range(rounds + 1):
+        for name, fn in variants.items():
+            for _ in range(3 if r else 8):
+                fn()
+            ms = host_timed(fn, calls)
+            if r:
+                times[name].append(ms)
+    total = eng.train_step(*ld.batch(indices()))[0]
+    assert torch.isfinite(total).item(), "the objective diverged"
+    med = {k: _median(v) for k, v in times.items()}
+    _emit(part="loader_step", shape=[N, 8, H, W], frame=[fh, fw], resident_mb=ld.resident_bytes() / 1e6, base_channels=BASE,
+          backbone=BACKBONE, rounds=rounds, ms_per_iteration=med, spread_ms={k: [min(v), max(v)] for k, v in times.items()},
+          loader_share_of_iteration=(med["loader_and_step"] - med["step_alone"]) / med["loader_and_step"],
+          last_total=total.item())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--part", default="all", choices=["all"] + list(LIMITS))
@@ -194,6 +270,8 @@ def main():
         part_objective(a.rounds, a.calls)
     elif a.part == "optim":
         part_optim(a.rounds, a.calls)
+    elif a.part == "loader_step":
+        part_loader_step(a.rounds, a.calls)
     else:
         part_step(a.rounds, a.calls, own=a.part == "step")
 
