@@ -54,7 +54,6 @@ class Plan(PlanConvMixin, PlanTuneMixin, PlanRunMixin):
         self.bn_bwd_fused = os.environ.get("PMF_BN_BWD_FUSED", "1") != "0"
         self._conv_fin = {}                 # forward conv op index -> index of the BN finalize op reading its rows
         self.n_wgrad = 0                    # weight-gradient ops emitted so far
-        import os as _os
         # lanes: independent branches of the network on separate HIP streams (csrc/plan.cpp); ``lane`` is the lane ops
         # are being emitted on; cross-lane edges are plan events (record after one op, wait before another)
         self.lane = 0
@@ -66,16 +65,16 @@ class Plan(PlanConvMixin, PlanTuneMixin, PlanRunMixin):
         # latency-bound ones.  (Round 2 measured this slower and kept it off: what it measured was the multi-branch
         # hipGraph replay, see csrc/plan.cpp; with the range replayed as linear pieces on real streams it is worth
         # 1.0 ms of 17.7 ms per step.)
-        self.wgrad_lane = int(_os.environ.get("PMF_WGRAD_LANE", "23"))
+        self.wgrad_lane = int(os.environ.get("PMF_WGRAD_LANE", "23"))
         self._wgrad_lane_of = (lambda home: 2 + (home & 1)) if self.wgrad_lane == 23 else (lambda home: self.wgrad_lane)
-        self.wgrad_batch = int(_os.environ.get("PMF_WGRAD_BATCH", "4"))
+        self.wgrad_batch = int(os.environ.get("PMF_WGRAD_BATCH", "4"))
         self._wg_deferred = {}
         self.n_events = 0
         self._event_pos = {}                # event -> list position of its record op
         self._last_op = {}                  # (id(op list), lane) -> last entry emitted on that lane
         self._pending_wait = {}             # (id(op list), lane) -> (event, position of its record op)
         self._touched = None                # gradient tensors touched by the tape entry being emitted
-        self.red_batch = int(_os.environ.get("PMF_RED_BATCH", str(RED_BATCH)))     # 0: one reduction op per layer
+        self.red_batch = int(os.environ.get("PMF_RED_BATCH", str(RED_BATCH)))     # 0: one reduction op per layer
         self.batch_reds = self.red_batch > 0
         self.pending_reds, self._red_tables = {}, []     # lane -> queued stage-2 reductions
         self.dp_events = []                 # (backward op count behind a batched reduction, [plan events]) -- see flush_reds
@@ -215,7 +214,7 @@ class Plan(PlanConvMixin, PlanTuneMixin, PlanRunMixin):
             for g in touched:
                 g._last_touch = (lane, last)
         for home in sorted(self._wg_deferred):
-            self.flush_wgrads(home, final=True)
+            self.flush_wgrads(home)
         for lane in sorted(self.pending_reds):
             self.flush_reds(lane)
         self.lane = 0
@@ -263,7 +262,7 @@ class Plan(PlanConvMixin, PlanTuneMixin, PlanRunMixin):
                 r.gy = T(self, r.t.N, r.t.H, r.t.W, r.t.C, r.t.name + ".gy", ldc=r.t.ldc)
             acc = r.gy_written
             r.gy_written = True
-            r._gy_last = None       # (_dgrad re-arms it when this writer can carry the BN-backward reduction)
+            r._gy_last = None       # (the BatchNorm carry is disarmed: PlanConvMixin._arm_bn_carry has the protocol)
             self._touch(r.gy)
             return r.gy, int(acc)
         t = r.t

@@ -10,6 +10,19 @@ from . import _lib as L
 from .plan_graph import COL_ROWS, SPLITK_BYTES, _ru, T, V
 
 
+def _sm(op, p=(), i=(), f=(), l=()):
+    """arguments of a small op: pointers, ints, floats and 64-bit ints, each from slot 0 on"""
+    a = op.u.sm
+    for slots, vals in ((a.p, p), (a.i, i), (a.f, f), (a.l, l)):
+        for k, v in enumerate(vals):
+            slots[k] = v
+
+
+def _class_hw(H, W, stride, py, px):
+    """the pixels of an H x W map that one input-gradient launch writes: all of them (stride 1) or one parity class"""
+    return (H, W) if stride == 1 else ((H - py + 1) // 2, (W - px + 1) // 2)
+
+
 class PlanConvMixin(object):
     def taps(self, kh, kw, dil, pad):
         out = []
@@ -45,35 +58,34 @@ class PlanConvMixin(object):
             return False
         return int(L.lib().pmf_conv_s3_eligible(C.byref(probe)))     # (3: the stem class, weights in pack format 2)
 
-    def conv(self, srcs, conv, act=L.ACT_NONE, bn=None, order="act_bn", relu_view=False, name="", pmask=None,
-             extra_bias=None):
-        """Conv2d (+bias) -> act -> [BatchNorm]  (order 'act_bn', SalsaNext style) or
-        Conv2d -> BatchNorm -> [ReLU on the view]  (order 'bn_act', ResNet / attention style).
-        Returns a V.  Registers the backward (BN backward, input gradients, weight gradient)."""
-        kh, kw = conv.kernel_size
-        dil, pad, stride = conv.dilation[0], conv.padding[0], conv.stride[0]
-        Cout = conv.out_channels
-        t0 = srcs[0].t
-        N = t0.N
-        inH = max(s.t.H for s in srcs)
-        inW = max(s.t.W for s in srcs)
-        OH = (inH + 2 * pad - dil * (kh - 1) - 1) // stride + 1
-        OW = (inW + 2 * pad - dil * (kw - 1) - 1) // stride + 1
-        out = T(self, N, OH, OW, Cout, name)
-        # taps that can only ever read zero padding (|offset| beyond the map: the dilation-12/18 ASPP branches on a
-        # 4-row map keep 3 of 9 taps) are dropped from forward, input gradient and weight gradient alike; their weight
-        # gradient is exactly zero and stays at the zero the backward prologue writes
+    def _live_taps(self, conv, inH, inW, OH, OW):
+        """(taps, gather) of a layer.  Taps that can only ever read zero padding (|offset| beyond the map: the dilation-12/18
+        ASPP branches on a 4-row map keep 3 of 9 taps) are dropped from forward, input gradient and weight gradient alike;
+        their weight gradient is exactly zero and stays at the zero the backward prologue writes."""
+        (kh, kw), dil, pad, stride = conv.kernel_size, conv.dilation[0], conv.padding[0], conv.stride[0]
         all_taps = self.taps(kh, kw, dil, pad)
         taps = [(dy, dx, wi) for (dy, dx, wi) in all_taps
                 if dy < inH and dy + (OH - 1) * stride >= 0 and dx < inW and dx + (OW - 1) * stride >= 0] or all_taps[:1]
-        Ktot = sum(_ru(s.t.C, 8) for s in srcs)
-        ldw = _ru(Cout, 64)
         # very large dilations: per-tap staging (the halo tile would not fit LDS)
         # (rows and columns separately: the dilation-12 / 18 ASPP branches keep one ROW of three taps on the 4-row map -- a
         # 4 x 56-pixel halo tile, not a 32 x 56 one)
         span_y = max(t[0] for t in taps) - min(t[0] for t in taps)
         span_x = max(t[1] for t in taps) - min(t[1] for t in taps)
-        gather = 1 if (8 * stride + span_y) * (32 * stride + span_x) * 80 > 110 * 1024 else 0
+        return taps, 1 if (8 * stride + span_y) * (32 * stride + span_x) * 80 > 110 * 1024 else 0
+
+    def conv(self, srcs, conv, act=L.ACT_NONE, bn=None, order="act_bn", relu_view=False, name="", pmask=None,
+             extra_bias=None):
+        """Conv2d (+bias) -> act -> [BatchNorm]  (order 'act_bn', SalsaNext style) or
+        Conv2d -> BatchNorm -> [ReLU on the view]  (order 'bn_act', ResNet / attention style).
+        Returns a V.  Registers the backward (BN backward, input gradients, weight gradient)."""
+        (kh, kw), dil, pad, stride = conv.kernel_size, conv.dilation[0], conv.padding[0], conv.stride[0]
+        Cout, N = conv.out_channels, srcs[0].t.N
+        inH = max(s.t.H for s in srcs)
+        inW = max(s.t.W for s in srcs)
+        OH = (inH + 2 * pad - dil * (kh - 1) - 1) // stride + 1
+        OW = (inW + 2 * pad - dil * (kw - 1) - 1) // stride + 1
+        out = T(self, N, OH, OW, Cout, name)
+        taps, gather = self._live_taps(conv, inH, inW, OH, OW)
         # a BatchNorm module in eval mode inside a training plan (frozen statistics, torch semantics): running statistics in
         # the forward pass, no statistics update, backward through the fixed affine map (dgamma / dbeta still flow)
         train_bn = bn is not None and self.training and bn.training
@@ -86,12 +98,36 @@ class PlanConvMixin(object):
             if not has_bias:
                 raise NotImplementedError("extra_bias needs a conv bias to add to")
             bsum = self.persist.alloc(4 * Cout)
+            self.emit(self.fwd, L.OP_VEC_ADD,
+                      lambda op: _sm(op, p=(conv.bias.data_ptr(), extra_bias.data_ptr(), bsum.ptr), i=(Cout,)))
+        stats, stat_rows = self._conv_forward(srcs, conv, out, taps, gather, k_act, bsum, pmask, train_bn, name)
+        view = self._bn_forward(out, bn, train_bn, stats, stat_rows, relu_view) if bn is not None else V(out)
+        if name:
+            self.views[name] = view
+            self.act_sites.append((conv, name, k_act, bool(relu_view)))
+        if not self.training:
+            return view
 
-            def fv(op):
-                a = op.u.sm
-                a.p[0], a.p[1], a.p[2] = conv.bias.data_ptr(), extra_bias.data_ptr(), bsum.ptr
-                a.i[0] = Cout
-            self.emit(self.fwd, L.OP_VEC_ADD, fv)
+        def backward():
+            # partial column sums of dz for the conv-bias gradient: one buffer PER LAYER (the weight-gradient op that
+            # folds them runs on the side stream while the main stream already works on the next layer)
+            dbr = self.act.alloc(COL_ROWS * _ru(Cout, 4) * 4) if (has_bias and pmask is None) else None
+            if bn is not None:
+                dz, dbias_rows = self._bn_backward(view, k_act, train_bn, dbr, name)
+            else:
+                dz, dbias_rows = self._act_backward(out, k_act, has_bias, dbr)
+            if pmask is not None:
+                self._mask_bias_backward(dz, pmask, conv, extra_bias)
+            self._dgrad(srcs, conv, dz, taps, stride, gather, name)
+            self._wgrad(srcs, conv, dz, taps, stride, gather, name, dbias_rows, dbr, _ru(Cout, 4))
+        self.on_backward(backward)
+        return view
+
+    def _conv_forward(self, srcs, conv, out, taps, gather, k_act, bsum, pmask, train_bn, name):
+        """the forward launch of a layer: kernel class and weight pack, the partial-statistics rows of a training BatchNorm
+        behind it, the op.  Returns (statistics rows buffer or None, the row count of the launch as built)."""
+        N, OH, OW, Cout, stride = out.N, out.H, out.W, out.C, conv.stride[0]
+        Ktot, ldw, has_bias = sum(_ru(s.t.C, 8) for s in srcs), _ru(Cout, 64), conv.bias is not None
 
         def shape_fill(d):
             d.N, d.OH, d.OW, d.Cout, d.nsrc = N, OH, OW, Cout, len(srcs)
@@ -113,7 +149,7 @@ class PlanConvMixin(object):
             wbuf = self.add_pack(conv.weight, [t[2] for t in taps], 0, _ru(len(taps) * 8, 16), ldw, 2)
         else:
             wbuf = self.add_pack(conv.weight, [t[2] for t in taps], 0, Ktot, ldw, int(bool(fwd_s3)))
-        stat_rows = 0
+        stat_rows, stats = 0, None
         if train_bn:
             probe = L.ConvDesc()
             shape_fill(probe)
@@ -121,12 +157,10 @@ class PlanConvMixin(object):
             stat_rows = L.lib().pmf_conv_fwd_stat_rows(C.byref(probe))
             # the autotuner (Plan.autotune) may pick another tile configuration: size the rows for any of them
             max_rows = max(stat_rows, L.lib().pmf_conv_fwd_stat_rows_max(C.byref(probe)))
-        stats = self.act.alloc(16 * Cout * max_rows) if train_bn else None   # float64 [rows][2][Cout] partials
-        bn_train_flag = int(train_bn)
-
+            stats = self.act.alloc(16 * Cout * max_rows)          # float64 [rows][2][Cout] partials
         lane = self.lane
 
-        def f(op, srcs=srcs):
+        def f(op):
             d = op.u.conv
             shape_fill(d)
             for i, s in enumerate(srcs):
@@ -139,208 +173,200 @@ class PlanConvMixin(object):
             d.bias = (bsum.ptr if bsum is not None else conv.bias.data_ptr()) if has_bias else None
             d.act = k_act
             d.out, d.out_ldc, d.out_H, d.out_W = out.buf.ptr, out.ldc, OH, OW
-            d.out_sy = d.out_sx = 1
             d.stats = stats.ptr if stats is not None else None
             d.ep_pmask = pmask.buf.ptr if pmask is not None else None
             d.splitk_ws, d.splitk_ws_bytes = self.sk_bufs[lane].ptr, self.sk_bufs[lane].nbytes
             d.splitk_tickets = self.sk_tickets[lane].ptr if self.sk_fused else None
         self.emit(self.fwd, L.OP_CONV, f)
-        conv_fwd_index = len(self.fwd) - 1
         conv_flops = 2.0 * N * OH * OW * Cout * conv.in_channels * len(taps)   # algorithmic (SURVEY.md 8d rule)
         self.meta_fwd[len(self.fwd) - 1] = dict(family="conv_fwd", flops=conv_flops, name=name, shape="%dx%dx%d %d->%d t%d s%d" % (
             N, OH, OW, conv.in_channels, Cout, len(taps), stride))
+        return stats, stat_rows
 
-        view = V(out)
-        info = None
-        if bn is not None:
-            Cb = Cout
-            scale, shift = self.persist.alloc(4 * Cb), self.persist.alloc(4 * Cb)
-            smean, sinv = self.persist.alloc(4 * Cb), self.persist.alloc(4 * Cb)
-            count = float(N * OH * OW)
-            if train_bn:
-                def fb(op):
-                    a = op.u.sm
-                    for i, p in enumerate((stats.ptr, bn.weight.data_ptr(), bn.bias.data_ptr(),
-                                           bn.running_mean.data_ptr(), bn.running_var.data_ptr(), scale.ptr,
-                                           shift.ptr, smean.ptr, sinv.ptr)):
-                        a.p[i] = p
-                    a.f[0], a.f[1], a.f[2] = count, bn.momentum, bn.eps
-                    a.i[0], a.i[1] = Cb, stat_rows
-                self.emit(self.fwd, L.OP_BN_FINALIZE, fb)
-                self._conv_fin[conv_fwd_index] = len(self.fwd) - 1      # its row count follows the conv's tile config
-            else:
-                def fb(op):
-                    a = op.u.sm
-                    for i, p in enumerate((bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
-                                           bn.running_var.data_ptr(), scale.ptr, shift.ptr, smean.ptr, sinv.ptr)):
-                        a.p[i] = p
-                    a.f[0] = bn.eps
-                    a.i[0] = Cb
-                self.emit(self.fwd, L.OP_BN_EVAL, fb)
-            info = dict(mean=smean, invstd=sinv, module=bn)
-            view = V(out, scale, shift, relu=relu_view, bn=info)
-            if train_bn:
-                self.bn_modules.append(bn)
-        if name:
-            self.views[name] = view
-            self.act_sites.append((conv, name, k_act, bool(relu_view)))
-        if not self.training:
-            return view
+    def _bn_forward(self, out, bn, train_bn, stats, stat_rows, relu_view):
+        """the BatchNorm behind the conv op just emitted: batch statistics from the conv's partial rows (training) or the
+        running statistics (eval) -> per-channel scale / shift; returns the view that applies them"""
+        Cb = out.C
+        scale, shift = self.persist.alloc(4 * Cb), self.persist.alloc(4 * Cb)
+        smean, sinv = self.persist.alloc(4 * Cb), self.persist.alloc(4 * Cb)
+        if train_bn:
+            self.emit(self.fwd, L.OP_BN_FINALIZE, lambda op: _sm(
+                op, p=(stats.ptr, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
+                       bn.running_var.data_ptr(), scale.ptr, shift.ptr, smean.ptr, sinv.ptr),
+                f=(float(out.npix), bn.momentum, bn.eps), i=(Cb, stat_rows)))
+            self._conv_fin[len(self.fwd) - 2] = len(self.fwd) - 1      # its row count follows the conv's tile config
+            self.bn_modules.append(bn)
+        else:
+            self.emit(self.fwd, L.OP_BN_EVAL, lambda op: _sm(
+                op, p=(bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
+                       scale.ptr, shift.ptr, smean.ptr, sinv.ptr), f=(bn.eps,), i=(Cb,)))
+        return V(out, scale, shift, relu=relu_view, bn=dict(mean=smean, invstd=sinv, module=bn))
 
-        # ------------------------------------------------------------------ backward
-        def backward():
-            # partial column sums of dz for the conv-bias gradient: one buffer PER LAYER (the weight-gradient op that
-            # folds them runs on the side stream while the main stream already works on the next layer)
-            dbr_ld = _ru(Cout, 4)
-            dbr = self.act.alloc(COL_ROWS * dbr_ld * 4) if (has_bias and pmask is None) else None
-            if bn is not None:
-                if getattr(view, "_side", None):
-                    if view.gy is None:
-                        view.gy = T(self, N, OH, OW, Cout, name + ".gy", ldc=out.ldc)
-                    view.gy_written = self._fold_side(view, view.gy, view.gy_written)
-                    view._side = None
-                    view._gy_last = None
-                if view.gy is None:
-                    raise RuntimeError("plan: no gradient reached BN output of %s" % name)
-                if out.g is None:
-                    out.g = T(self, N, OH, OW, Cout, name + ".dz", ldc=out.ldc)
-                out.g_written = True
-                coef = self.act.alloc(12 * Cout)                  # [3][Cout] per-channel backward coefficients
-                dgam, dbet = self.pgrad(bn.weight), self.pgrad(bn.bias)
-                gyt, dz = view.gy, out.g
-                self._touch(gyt)
-                self._touch(dz)
-                self.colrows_max = max(self.colrows_max, _ru(Cout, 4))
+    # ------------------------------------------------------------------ backward of a layer: dL/d(conv output)
+    def _bn_backward(self, view, k_act, train_bn, dbr, name):
+        """BatchNorm (+ activation) backward: view.gy, the gradient w.r.t. the BatchNorm output -> out.g, the gradient w.r.t. the
+        conv output.  Returns (out.g, number of partial conv-bias-gradient rows written to dbr)."""
+        out, bn, mean, invstd = view.t, view.bn["module"], view.bn["mean"], view.bn["invstd"]
+        Cout, lane, flag = out.C, self.lane, int(train_bn)
+        if getattr(view, "_side", None):
+            if view.gy is None:
+                view.gy = T(self, out.N, out.H, out.W, Cout, name + ".gy", ldc=out.ldc)
+            view.gy_written = self._fold_side(view, view.gy, view.gy_written)
+            view._side = None
+            view._gy_last = None
+        if view.gy is None:
+            raise RuntimeError("plan: no gradient reached BN output of %s" % name)
+        if out.g is None:
+            out.g = T(self, out.N, out.H, out.W, Cout, name + ".dz", ldc=out.ldc)
+        out.g_written = True
+        coef = self.act.alloc(12 * Cout)                  # [3][Cout] per-channel backward coefficients
+        dgam, dbet = self.pgrad(bn.weight), self.pgrad(bn.bias)
+        gyt, dz = view.gy, out.g
+        self._touch(gyt)
+        self._touch(dz)
+        self.colrows_max = max(self.colrows_max, _ru(Cout, 4))
+        # dgamma and dbeta are complete after the first op emitted below
+        self.grad_done[id(bn.weight)] = self.grad_done[id(bn.bias)] = len(self.bwd)
+        carry = getattr(view, "_gy_last", None)
+        if (os.environ.get("PMF_BN_SMALL", "1") != "0" and Cout % 4 == 0
+                and bool(L.lib().pmf_bn_bwd_small_ok(out.npix, Cout))):
+            # small maps (<= 2048 pixels: the 4x128 stage and below, a fifth of the BatchNorm layers): column sums,
+            # fold and apply in ONE launch (bn.hip bn_bwd_small_k) instead of three latency-bound ones; the
+            # input-gradient epilogue then carries no partial sums either (its hook stays empty)
+            self.emit(self.bwd, L.OP_BN_BWD_SMALL, lambda op: _sm(
+                op, p=(gyt.buf.ptr, out.buf.ptr, mean.ptr, bn.weight.data_ptr(), invstd.ptr, dz.buf.ptr,
+                       dbr.ptr if dbr is not None else None, self.pgrad_buf.at(dgam), self.pgrad_buf.at(dbet)),
+                i=(gyt.ldc, out.ldc, Cout, flag, k_act, dz.ldc), l=(out.npix,)))
+            self.note_bytes(self.bwd, "bn_bwd_small", 12.0 * out.npix * Cout)
+            return dz, 1 if dbr is not None else 0
+        if carry is not None and carry["lane"] == lane:
+            self._bn_bwd_fold(view, carry, coef, dgam, dbet, flag)
+        else:
+            self.emit(self.bwd, L.OP_BN_BWD_REDUCE, lambda op: _sm(
+                op, p=(gyt.buf.ptr, out.buf.ptr, mean.ptr, bn.weight.data_ptr(), invstd.ptr, self.bnpart_bufs[lane].ptr,
+                       coef.ptr, self.pgrad_buf.at(dgam), self.pgrad_buf.at(dbet)),
+                i=(gyt.ldc, out.ldc, Cout, flag), l=(out.npix,)))
+            self.note_bytes(self.bwd, "bn_bwd_reduce", 8.0 * out.npix * Cout)
+        self.emit(self.bwd, L.OP_BN_BWD_APPLY, lambda op: _sm(
+            op, p=(gyt.buf.ptr, out.buf.ptr, coef.ptr, mean.ptr, dz.buf.ptr, dbr.ptr if dbr is not None else None),
+            i=(gyt.ldc, out.ldc, Cout, k_act, dz.ldc, _ru(Cout, 4)), l=(out.npix,)))
+        self.note_bytes(self.bwd, "bn_bwd_apply", 12.0 * out.npix * Cout)
+        return dz, L.lib().pmf_col_rows(out.npix, Cout) if dbr is not None else 0
 
-                lw = getattr(view, "_gy_last", None)
-                # small maps (<= 2048 pixels: the 4x128 stage and below, a fifth of the BatchNorm layers): column sums,
-                # fold and apply in ONE launch (bn.hip bn_bwd_small_k) instead of three latency-bound ones; the
-                # input-gradient epilogue then carries no partial sums either (its hook stays empty)
-                small = (os.environ.get("PMF_BN_SMALL", "1") != "0" and Cout % 4 == 0
-                         and bool(L.lib().pmf_bn_bwd_small_ok(out.npix, Cout)))
-                if small:
-                    one_row = has_bias and pmask is None
+    def _arm_bn_carry(self, r, tgt, hook, shape):
+        """The BatchNorm carry.  An input-gradient launch that is the LAST writer of the output gradient of a BatchNorm view
+        (r.gy) also writes, from its epilogue, the partial column sums that layer's BatchNorm backward needs (sum gy and
+        sum gy * (a - mean), one float64 row per output tile); the layer then needs no reduction pass over gy, only the fold.
+          * Armed here, by _dgrad_merged and _dgrad_launch, right after they emit a stride-1 launch that writes r.gy itself
+            (not a broadcast temporary or another lane's private accumulator): r._gy_last = the launch's still empty hook,
+            its op index, its shape filler and its lane.
+          * Disarmed by Plan.grad_of: whoever asks for r.gy next is its new last writer (a conv re-arms after its launch, an
+            element-wise backward cannot carry the sums); and by _bn_backward when it folds other lanes' accumulators in.
+          * Consumed by _bn_bwd_fold when the backward of the layer that produced r is emitted.  It sizes the row buffer with
+            the launch's own shape filler -- the row count is the kernel selection's, and a count computed for another kernel
+            than the one launched is an out-of-bounds write or uninitialised rows in the sums --, puts the buffer and the
+            saved mean into the hook, which _dgrad_epilogue wires into the launch when the plan is finalised, and emits
+            OP_BN_BWD_FOLD over the rows.  One-launch BatchNorm backwards (small maps) leave the hook empty.
+          * _conv_fold[launch index] lists the fold ops that read a launch's rows (a merged launch feeds one per
+            destination): a tile configuration written into the launch later changes its row count, and plan_tune.py
+            rewrites the folds' counts through this map.
+          * The lane must match: launch and fold hand the rows over in the stream order of one lane, no event in between.
+            grad_of gives r.gy itself only to consumers on the producer's lane, so the consumer's test is a guard."""
+        if r.bn is not None and tgt is r.gy and self.bn_bwd_fused:
+            r._gy_last = dict(hook=hook, index=len(self.bwd) - 1, shape=shape, lane=self.lane)
 
-                    def rs(op):
-                        a = op.u.sm
-                        ps = (gyt.buf.ptr, out.buf.ptr, info["mean"].ptr, bn.weight.data_ptr(), info["invstd"].ptr,
-                              dz.buf.ptr, dbr.ptr if (dbr is not None and one_row) else None, self.pgrad_buf.at(dgam),
-                              self.pgrad_buf.at(dbet))
-                        for i, p in enumerate(ps):
-                            a.p[i] = p
-                        a.i[0], a.i[1], a.i[2], a.i[3], a.i[4], a.i[5] = gyt.ldc, out.ldc, Cout, bn_train_flag, k_act, dz.ldc
-                        a.l[0] = out.npix
-                    self.emit(self.bwd, L.OP_BN_BWD_SMALL, rs)
-                    self.note_bytes(self.bwd, "bn_bwd_small", 12.0 * out.npix * Cout)
-                    self.grad_done[id(bn.weight)] = self.grad_done[id(bn.bias)] = len(self.bwd) - 1
-                    dbias_rows = 1 if one_row else 0
-                elif lw is not None and lw["lane"] == lane:
-                    # the last writer of gy was an input-gradient launch on this lane: it carried the reduction
-                    # (sum gy, sum gy*(a - mean) per tile row) in its epilogue; only the fold is left
-                    probe = L.ConvDesc()
-                    lw["shape"](probe)
-                    nrows = L.lib().pmf_conv_fwd_stat_rows(C.byref(probe))
-                    rows = self.act.alloc(16 * Cout * max(nrows, L.lib().pmf_conv_fwd_stat_rows_max(C.byref(probe))))
-                    lw["hook"].update(rows=rows, mean=info["mean"])
+    def _bn_bwd_fold(self, view, carry, coef, dgam, dbet, flag):
+        """consumer of the BatchNorm carry (_arm_bn_carry): the last writer of view.gy was an input-gradient launch on this
+        lane that carries the reduction in its epilogue; only the fold of its partial rows is left"""
+        out, bn, Cout = view.t, view.bn["module"], view.t.C
+        probe = L.ConvDesc()
+        carry["shape"](probe)
+        nrows = L.lib().pmf_conv_fwd_stat_rows(C.byref(probe))
+        rows = self.act.alloc(16 * Cout * max(nrows, L.lib().pmf_conv_fwd_stat_rows_max(C.byref(probe))))
+        carry["hook"].update(rows=rows, mean=view.bn["mean"])
+        self.emit(self.bwd, L.OP_BN_BWD_FOLD, lambda op: _sm(
+            op, p=(rows.ptr, bn.weight.data_ptr(), view.bn["invstd"].ptr, coef.ptr, self.pgrad_buf.at(dgam),
+                   self.pgrad_buf.at(dbet)), i=(Cout, nrows, flag), l=(out.npix,)))
+        self._conv_fold.setdefault(carry["index"], []).append(len(self.bwd) - 1)
 
-                    def r1(op):
-                        a = op.u.sm
-                        ps = (rows.ptr, bn.weight.data_ptr(), info["invstd"].ptr, coef.ptr, self.pgrad_buf.at(dgam),
-                              self.pgrad_buf.at(dbet))
-                        for i, p in enumerate(ps):
-                            a.p[i] = p
-                        a.i[0], a.i[1], a.i[2] = Cout, nrows, bn_train_flag
-                        a.l[0] = out.npix
-                    self.emit(self.bwd, L.OP_BN_BWD_FOLD, r1)
-                    self._conv_fold.setdefault(lw["index"], []).append(len(self.bwd) - 1)     # (a multi-destination
-                    #                                                      launch feeds one fold per destination)
-                else:
-                    def r1(op):
-                        a = op.u.sm
-                        ps = (gyt.buf.ptr, out.buf.ptr, info["mean"].ptr, bn.weight.data_ptr(), info["invstd"].ptr,
-                              self.bnpart_bufs[lane].ptr, coef.ptr, self.pgrad_buf.at(dgam), self.pgrad_buf.at(dbet))
-                        for i, p in enumerate(ps):
-                            a.p[i] = p
-                        a.i[0], a.i[1], a.i[2], a.i[3] = gyt.ldc, out.ldc, Cout, bn_train_flag
-                        a.l[0] = out.npix
-                    self.emit(self.bwd, L.OP_BN_BWD_REDUCE, r1)
-                    self.note_bytes(self.bwd, "bn_bwd_reduce", 8.0 * out.npix * Cout)
-                if not small:
-                    self.grad_done[id(bn.weight)] = self.grad_done[id(bn.bias)] = len(self.bwd) - 1
+    def _act_backward(self, out, k_act, has_bias, dbr):
+        """no BatchNorm: the activation derivative in place on out.g, and the partial rows of the conv-bias gradient"""
+        dz, C4 = self.tgrad(out), _ru(out.C, 4)
+        if k_act == L.ACT_NONE and not has_bias:
+            return dz, 0
+        self.emit(self.bwd, L.OP_ACT_BWD, lambda op: _sm(
+            op, p=(dz.buf.ptr, out.buf.ptr, dbr.ptr if dbr is not None else None),
+            i=(dz.ldc, out.ldc, k_act, C4, C4), l=(out.npix,)))
+        self.note_bytes(self.bwd, "act_bwd", 12.0 * out.npix * out.C)
+        return dz, L.lib().pmf_col_rows(out.npix, C4) if dbr is not None else 0
 
-                def r2(op):
-                    a = op.u.sm
-                    ps = (gyt.buf.ptr, out.buf.ptr, coef.ptr, info["mean"].ptr, dz.buf.ptr,
-                          dbr.ptr if dbr is not None else None)
-                    for i, p in enumerate(ps):
-                        a.p[i] = p
-                    a.i[0], a.i[1], a.i[2], a.i[3], a.i[4], a.i[5] = gyt.ldc, out.ldc, Cout, k_act, dz.ldc, dbr_ld
-                    a.l[0] = out.npix
-                if not small:
-                    self.emit(self.bwd, L.OP_BN_BWD_APPLY, r2)
-                    self.note_bytes(self.bwd, "bn_bwd_apply", 12.0 * out.npix * Cout)
-                    dbias_rows = L.lib().pmf_col_rows(out.npix, Cout) if (has_bias and pmask is None) else 0
-            else:
-                dz = self.tgrad(out)
-                dbias_rows = 0
-                if k_act != L.ACT_NONE or has_bias:
-                    def r3(op):
-                        a = op.u.sm
-                        a.p[0], a.p[1] = dz.buf.ptr, out.buf.ptr
-                        a.p[2] = dbr.ptr if dbr is not None else None
-                        a.i[0], a.i[1], a.i[2], a.i[3], a.i[4] = dz.ldc, out.ldc, k_act, _ru(Cout, 4), dbr_ld
-                        a.l[0] = out.npix
-                    self.emit(self.bwd, L.OP_ACT_BWD, r3)
-                    self.note_bytes(self.bwd, "act_bwd", 12.0 * out.npix * Cout)
-                    dbias_rows = L.lib().pmf_col_rows(out.npix, _ru(Cout, 4)) if (has_bias and pmask is None) else 0
-            dz = out.g
-            if pmask is not None:
-                # d/dz of act(z) * m: the activation derivative above was taken from a = act(z)*m (slope of the
-                # masked-out zeros is irrelevant) -- multiply by the mask, then the bias gradients are plain column
-                # sums of the masked dz (both bias vectors of SparseVariantConv receive the same gradient)
-                def rm(op, dz=dz):
-                    a = op.u.sm
-                    a.p[0], a.p[1], a.p[2] = dz.buf.ptr, pmask.buf.ptr, dz.buf.ptr
-                    a.i[0], a.i[1], a.i[2], a.i[3] = dz.ldc, _ru(Cout, 4), dz.ldc, 0
-                    a.l[0] = dz.npix
-                self.emit(self.bwd, L.OP_PMASK_MUL_BWD, rm)
-                if has_bias:
-                    boff = self.pgrad(conv.bias)
+    def _mask_bias_backward(self, dz, pmask, conv, extra_bias):
+        """d/dz of act(z) * m: the activation derivative was taken from a = act(z)*m (slope of the masked-out zeros is
+        irrelevant) -- multiply by the mask, then the bias gradients are plain column sums of the masked dz (both bias
+        vectors of SparseVariantConv receive the same gradient)"""
+        Cout = dz.C
+        self.emit(self.bwd, L.OP_PMASK_MUL_BWD, lambda op: _sm(
+            op, p=(dz.buf.ptr, pmask.buf.ptr, dz.buf.ptr), i=(dz.ldc, _ru(Cout, 4), dz.ldc, 0), l=(dz.npix,)))
+        if conv.bias is None:
+            return
+        boff = self.pgrad(conv.bias)
+        crows = self.act.alloc(COL_ROWS * _ru(Cout, 4) * 4)      # partial rows of the deterministic column sum
+        self.emit(self.bwd, L.OP_COLSUM, lambda op: _sm(
+            op, p=(dz.buf.ptr, self.pgrad_buf.at(boff), crows.ptr), i=(dz.ldc, Cout, 1), l=(dz.npix,)))
+        self.grad_done[id(conv.bias)] = len(self.bwd) - 1
+        if extra_bias is not None:
+            eoff = self.pgrad(extra_bias)
+            self.emit(self.bwd, L.OP_VEC_ADD, lambda op: _sm(
+                op, p=(self.pgrad_buf.at(boff), None, self.pgrad_buf.at(eoff)), i=(Cout,)))
+            self.grad_done[id(extra_bias)] = len(self.bwd) - 1
 
-                    crows = self.act.alloc(COL_ROWS * _ru(Cout, 4) * 4)      # partial rows of the deterministic column sum
+    # ------------------------------------------------------------------ input gradients
+    def _dgrad_shape(self, d, dz, Kd, gather, sub, H, W, Cdst, out_stride=None, w_s3=False, dst_C=(), splitk=False):
+        """the shape of an input-gradient launch -- what the kernel selection reads -- for probes and launches alike: dz
+        (Kd channels) through the taps ``sub`` onto an H x W map of Cdst channels.  The keywords are what the sites differ in:
+        the output stride, the split-bf16 marker, the channel counts of a merged launch's destinations, and the non-NULL
+        split-K fields (same split decision, hence the same partial-statistics row count, as the real launch)."""
+        d.N, d.OH, d.OW, d.Cout, d.nsrc = dz.N, H, W, Cdst, 1
+        sv = d.src[0]
+        sv.C, sv.ldc, sv.H, sv.W = Kd, dz.ldc, dz.H, dz.W
+        d.ntaps = len(sub)
+        for i, (dy, dx, _) in enumerate(sub):
+            d.tdy[i], d.tdx[i] = dy, dx
+        d.in_stride, d.gather = 1, gather
+        if out_stride:
+            d.out_sy = d.out_sx = out_stride
+        if w_s3:
+            d.w_s3 = 1
+        d.ndst = len(dst_C)
+        for k, c in enumerate(dst_C):
+            d.dst[k].C = c
+        if splitk:
+            d.splitk_ws, d.splitk_ws_bytes = 1, SPLITK_BYTES
+            d.splitk_tickets = 1 if self.sk_fused else None
 
-                    def rb(op, dz=dz, boff=boff, crows=crows):
-                        a = op.u.sm
-                        a.p[0], a.p[1], a.p[2] = dz.buf.ptr, self.pgrad_buf.at(boff), crows.ptr
-                        a.i[0], a.i[1], a.i[2] = dz.ldc, Cout, 1
-                        a.l[0] = dz.npix
-                    self.emit(self.bwd, L.OP_COLSUM, rb)
-                    self.grad_done[id(conv.bias)] = len(self.bwd) - 1
-                    if extra_bias is not None:
-                        eoff = self.pgrad(extra_bias)
-
-                        def re(op, boff=boff, eoff=eoff):
-                            a = op.u.sm
-                            a.p[0], a.p[1], a.p[2] = self.pgrad_buf.at(boff), None, self.pgrad_buf.at(eoff)
-                            a.i[0] = Cout
-                        self.emit(self.bwd, L.OP_VEC_ADD, re)
-                        self.grad_done[id(extra_bias)] = len(self.bwd) - 1
-            self._dgrad(srcs, conv, dz, taps, stride, gather, name)
-            self._wgrad(srcs, conv, dz, taps, stride, gather, name, dbias_rows, dbr, dbr_ld)
-        self.on_backward(backward)
-        return view
+    def _dgrad_epilogue(self, e, s, tgt, acc, hook):
+        """where and how an input-gradient launch writes the gradient of operand ``s``; ``e`` is the descriptor itself or one
+        destination of a merged launch (pmf_conv_dst_t: the same field names).  accumulate / Dropout2d multiplier / ReLU
+        mask of the operand's view / from a filled hook, the BatchNorm-backward partial sums (_arm_bn_carry)."""
+        r = s.root()
+        e.out, e.out_ldc, e.accumulate = tgt.buf.ptr, tgt.ldc, acc
+        if s.cmul is not None:
+            e.ep_cmul, e.ep_cmul_ld = self.masks_ptr + 4 * s.cmul, s.cmul_ld
+        if r.relu:
+            e.ep_relu_x, e.ep_relu_ldc = r.t.buf.ptr, r.t.ldc
+            e.ep_relu_scale = r.scale.ptr if r.scale is not None else None
+            e.ep_relu_shift = r.shift.ptr if r.shift is not None else None
+        if hook:
+            e.stats, e.ep_stat_mean = hook["rows"].ptr, hook["mean"].ptr
+            if not r.relu:
+                e.ep_relu_x, e.ep_relu_ldc, e.ep_flags = r.t.buf.ptr, r.t.ldc, L.EP_STAT_X_ONLY
 
     def _dgrad(self, srcs, conv, dz, taps, stride, gather, name):
         """input gradients: the same implicit-GEMM kernel run over dz with transposed weights.
         stride 1:  dX[y] = sum_t dz[y - dy_t] W_t^T                      (one launch per operand)
         stride 2:  y = 2m + py:  dX[y] = sum_{t: (py-dy_t) even} dz[m + (py-dy_t)/2] W_t^T   (one launch per parity)"""
-        Cout = conv.out_channels
-        Kd = _ru(Cout, 8)                       # K of the input-gradient GEMM (padded channels of dz are zero)
-        Cin_tot = sum(_ru(s.t.C, 8) for s in srcs)
         if not any(s.t.needs_grad for s in srcs):
             return
-        ldwT = _ru(Cin_tot, 64) + 64
-        lane = self.lane
         if stride == 1:
             classes = [(0, 0, [(-dy, -dx, wi) for (dy, dx, wi) in taps])]
         else:
@@ -351,6 +377,41 @@ class PlanConvMixin(object):
                            if (py - dy) % 2 == 0 and (px - dx) % 2 == 0]
                     if sub:
                         classes.append((py, px, sub))
+        ldwT = _ru(sum(_ru(s.t.C, 8) for s in srcs), 64) + 64
+        Kd, dg_s3, packs = self._dgrad_packs(srcs, conv, dz, classes, stride, gather, ldwT)
+        if (stride == 1 and packs is not None and all(dg_s3)
+                and self._dgrad_merged(srcs, conv, dz, Kd, gather, classes[0][2], packs[0], ldwT, name)):
+            return
+        coloff = 0
+        for s in srcs:
+            Cs = _ru(s.t.C, 8)
+            if s.t.needs_grad:
+                if packs is None:
+                    own_ld = _ru(Cs, 64) + 64
+                    own = [self.add_pack(conv.weight, [t[2] for t in sub], 1, Kd, own_ld, 1, cin=(coloff, Cs))
+                           for (_, _, sub) in classes]
+                    self._dgrad_operand(s, conv, dz, Kd, gather, stride, classes, dg_s3, own, own_ld, 0, name)
+                else:
+                    self._dgrad_operand(s, conv, dz, Kd, gather, stride, classes, dg_s3, packs, ldwT, coloff, name)
+            coloff += Cs
+
+    def _dgrad_packs(self, srcs, conv, dz, classes, stride, gather, ldwT):
+        """(K of the input-gradient GEMM, per parity class whether it runs on the split-bf16 kernels, the transposed weight pack
+        of every class -- or None: every operand gets packs of its own channel range, see below)"""
+        Cout = conv.out_channels
+        Kd = _ru(Cout, 8)                       # (padded channels of dz are zero)
+        ref = next(s for s in srcs if s.t.needs_grad)
+
+        def s3(Kd):
+            return [Kd % 16 == 0 and self.s3_ok(lambda d: self._dgrad_shape(
+                d, dz, Kd, gather, sub, *_class_hw(ref.t.H, ref.t.W, stride, py, px), ref.t.C)) for (py, px, sub) in classes]
+        if Kd % 16 and self.s3:
+            # 20 output channels (the logits heads): K = 24 keeps the launch off the split kernels.  Rounded up to 32 the last
+            # eight "channels" of a pixel are the first eight of the next pixel (finite values; past the end of the tensor the
+            # buffer range check returns 0) against weight rows that are zero -- they add exactly 0
+            if all(s3(_ru(Cout, 16))):
+                Kd = _ru(Cout, 16)
+        dg_s3 = s3(Kd)
         # split-bf16 launches address the transposed weights by 32-column fragments: every operand that receives a
         # gradient must start on one
         offs, co_ = [], 0
@@ -358,212 +419,118 @@ class PlanConvMixin(object):
             offs.append(co_)
             co_ += _ru(s.t.C, 8)
         aligned = all(o % 32 == 0 for o, s in zip(offs, srcs) if s.t.needs_grad)
-        ref = next(s for s in srcs if s.t.needs_grad)
-
-        def class_probe(sub, py, px):
-            def fill(d):
-                H, W = ref.t.H, ref.t.W
-                d.N = dz.N
-                d.OH, d.OW = (H, W) if stride == 1 else ((H - py + 1) // 2, (W - px + 1) // 2)
-                d.Cout, d.nsrc = ref.t.C, 1
-                sv = d.src[0]
-                sv.C, sv.ldc, sv.H, sv.W = Kd, dz.ldc, dz.H, dz.W
-                d.ntaps = len(sub)
-                for i, (dy, dx, _) in enumerate(sub):
-                    d.tdy[i], d.tdx[i] = dy, dx
-                d.in_stride, d.gather = 1, gather
-            return fill
-        if Kd % 16 and self.s3:
-            # 20 output channels (the logits heads): K = 24 keeps the launch off the split kernels.  Rounded up to 32 the last
-            # eight "channels" of a pixel are the first eight of the next pixel (finite values; past the end of the tensor the
-            # buffer range check returns 0) against weight rows that are zero -- they add exactly 0
-            Kd8, Kd = Kd, _ru(Cout, 16)
-            if not all(self.s3_ok(class_probe(sub, py, px)) for (py, px, sub) in classes):
-                Kd = Kd8
-        dg_s3 = [Kd % 16 == 0 and self.s3_ok(class_probe(sub, py, px)) for (py, px, sub) in classes]
         # operands that do not start on a 32-column fragment (16 + 64 channels): every operand gets its own transposed
         # pack of its channel range, starting at column 0
-        own_packs = not aligned and all(dg_s3) and all(_ru(s.t.C, 8) == s.t.C for s in srcs)
-        if not aligned and not own_packs:
+        if not aligned and all(dg_s3) and all(_ru(s.t.C, 8) == s.t.C for s in srcs):
+            return Kd, dg_s3, None
+        if not aligned:
             dg_s3 = [False] * len(classes)
-        packs = None if own_packs else [self.add_pack(conv.weight, [t[2] for t in sub], 1, Kd, ldwT, int(k3))
-                                        for (_, _, sub), k3 in zip(classes, dg_s3)]
-        # ---- one launch for all operands of a concatenated input (stride 1, split-bf16 path, every operand a whole number
-        # of 32-channel fragments): dz is read ONCE and the output-channel ranges go to the operands' gradient tensors, each
-        # with its own epilogue (accumulate / Dropout2d multiplier / ReLU mask / BatchNorm-backward partial sums)
-        merged = (stride == 1 and len(srcs) >= 2 and not own_packs and aligned and all(dg_s3) and len(srcs) <= L.MAX_SRC
-                  and all(s.t.needs_grad and not s.bcast and s.t.C % 32 == 0 for s in srcs)
-                  and dz.N * dz.H * dz.W >= int(os.environ.get("PMF_DGRAD_MERGE_MINPIX", "1024")) and os.environ.get("PMF_DGRAD_MERGE", "1") != "0")
-        if merged:
-            # torch.cat of one tensor (or one root) twice: two destinations would be ONE gradient buffer, written with
-            # accumulate 0 and 1 by workgroups of one launch in unspecified order -- such a concat keeps the per-operand
-            # launches (stream order)
-            holders = [(s.root() if s.root().bn is not None else s.root().t) for s in srcs]
-            merged = len({id(h_) for h_ in holders}) == len(holders)
-        if merged:
-            # the library's own eligibility rule, on the shape-only descriptor (a mismatch would otherwise only surface as
-            # PMF_E_ARG when the plan runs)
-            probe = L.ConvDesc()
-            probe.N, probe.OH, probe.OW = dz.N, ref.t.H, ref.t.W
-            probe.Cout, probe.nsrc = sum(s.t.C for s in srcs), 1
-            probe.src[0].C, probe.src[0].ldc, probe.src[0].H, probe.src[0].W = Kd, dz.ldc, dz.H, dz.W
-            probe.ntaps = len(classes[0][2])
-            for i, (dy, dx, _) in enumerate(classes[0][2]):
-                probe.tdy[i], probe.tdx[i] = dy, dx
-            probe.in_stride, probe.gather, probe.out_sy, probe.out_sx, probe.w_s3 = 1, gather, 1, 1, 1
-            probe.ndst = len(srcs)
-            for k_, s in enumerate(srcs):
-                probe.dst[k_].C = s.t.C
-            merged = bool(L.lib().pmf_conv_multi_ok(C.byref(probe)))
-        if merged:
-            (_, _, sub), wT = classes[0], packs[0]
-            parts = []
-            for s in srcs:
-                r = s.root()
-                tgt, acc = self.grad_of(s)
-                parts.append(dict(s=s, r=r, tgt=tgt, acc=acc, relu_x=(r.t if r.relu else None), hook={}))
-            Ctot = sum(pt["s"].t.C for pt in parts)
+        return Kd, dg_s3, [self.add_pack(conv.weight, [t[2] for t in sub], 1, Kd, ldwT, int(k3))
+                           for (_, _, sub), k3 in zip(classes, dg_s3)]
 
-            def shape_only(d, sub=sub, parts=parts, Ctot=Ctot):
-                d.N, d.OH, d.OW = dz.N, ref.t.H, ref.t.W
-                d.Cout, d.nsrc = Ctot, 1
-                sv = d.src[0]
-                sv.C, sv.ldc, sv.H, sv.W = Kd, dz.ldc, dz.H, dz.W
-                d.ntaps = len(sub)
-                for i, (dy, dx, _) in enumerate(sub):
-                    d.tdy[i], d.tdx[i] = dy, dx
-                d.in_stride, d.gather = 1, gather
-                d.out_sy = d.out_sx = 1
-                d.w_s3 = 1
-                d.ndst = len(parts)
-                for k, pt in enumerate(parts):
-                    d.dst[k].C = pt["s"].t.C
+    def _dgrad_merged(self, srcs, conv, dz, Kd, gather, sub, wT, ldwT, name):
+        """one launch for all operands of a concatenated input (stride 1, split-bf16 path, every operand a whole number of
+        32-channel fragments): dz is read ONCE and the output-channel ranges go to the operands' gradient tensors, each
+        with its own epilogue.  Returns False, with nothing allocated or emitted, where the launch does not apply."""
+        if not (2 <= len(srcs) <= L.MAX_SRC and all(s.t.needs_grad and not s.bcast and s.t.C % 32 == 0 for s in srcs)
+                and dz.N * dz.H * dz.W >= int(os.environ.get("PMF_DGRAD_MERGE_MINPIX", "1024"))
+                and os.environ.get("PMF_DGRAD_MERGE", "1") != "0"):
+            return False
+        # torch.cat of one tensor (or one root) twice: two destinations would be ONE gradient buffer, written with
+        # accumulate 0 and 1 by workgroups of one launch in unspecified order -- such a concat keeps the per-operand
+        # launches (stream order)
+        if len({id(s.root() if s.root().bn is not None else s.root().t) for s in srcs}) != len(srcs):
+            return False
+        H, W, chans = srcs[0].t.H, srcs[0].t.W, [s.t.C for s in srcs]
 
-            def f(op, parts=parts, wT=wT, shape_only=shape_only, ldwT=ldwT):
-                d = op.u.conv
-                shape_only(d)
-                d.src[0].x = dz.buf.ptr
-                d.ldw = ldwT
-                d.w_s3 = wT.ptr
-                d.act = L.ACT_NONE
-                d.out_H, d.out_W = ref.t.H, ref.t.W
-                d.out, d.out_ldc = parts[0]["tgt"].buf.ptr, parts[0]["tgt"].ldc
-                for k, pt in enumerate(parts):
-                    e, s, r, tgt = d.dst[k], pt["s"], pt["r"], pt["tgt"]
-                    e.out, e.out_ldc, e.accumulate = tgt.buf.ptr, tgt.ldc, pt["acc"]
-                    if s.cmul is not None:
-                        e.ep_cmul, e.ep_cmul_ld = self.masks_ptr + 4 * s.cmul, s.cmul_ld
-                    if pt["relu_x"] is not None:
-                        e.ep_relu_x, e.ep_relu_ldc = pt["relu_x"].buf.ptr, pt["relu_x"].ldc
-                        e.ep_relu_scale = r.scale.ptr if r.scale is not None else None
-                        e.ep_relu_shift = r.shift.ptr if r.shift is not None else None
-                    if pt["hook"]:
-                        e.stats, e.ep_stat_mean = pt["hook"]["rows"].ptr, pt["hook"]["mean"].ptr
-                        if pt["relu_x"] is None:
-                            e.ep_relu_x, e.ep_relu_ldc, e.ep_flags = r.t.buf.ptr, r.t.ldc, L.EP_STAT_X_ONLY
-            self.emit(self.bwd, L.OP_CONV, f)
-            for pt in parts:
-                r = pt["r"]
-                if r.bn is not None and pt["tgt"] is r.gy and self.bn_bwd_fused:
-                    r._gy_last = dict(hook=pt["hook"], index=len(self.bwd) - 1, shape=shape_only, lane=lane)
-            self.meta_bwd[len(self.bwd) - 1] = dict(
-                family="conv_dgrad", flops=2.0 * dz.N * ref.t.H * ref.t.W * Ctot * Cout * len(sub), name=name,
-                shape="%dx%dx%d %d->%s t%d s1" % (dz.N, ref.t.H, ref.t.W, Cout, "+".join(str(pt["s"].t.C) for pt in parts),
-                                                  len(sub)))
-            return
-        coloff = 0
-        for s in srcs:
-            Cs = _ru(s.t.C, 8)
-            if s.t.needs_grad:
-                if own_packs:
-                    ldwT = _ru(Cs, 64) + 64
-                    packs = [self.add_pack(conv.weight, [t[2] for t in sub], 1, Kd, ldwT, 1, cin=(coloff, Cs))
-                             for (_, _, sub) in classes]
-                r = s.root()
-                tmp = None
-                if s.bcast:
-                    # 1x1 map broadcast over the image: full-size gradient into a temp, then per-sample column sums
-                    tmp = T(self, dz.N, dz.H, dz.W, s.t.C, name + ".bcast_tmp")
-                    if r.t.g is None:
-                        r.t.g = T(self, r.t.N, 1, 1, r.t.C, r.t.name + ".g", arena=self.zero_bwd, ldc=r.t.ldc)
-                    r.t.g_written = True
-                    self._touch(r.t.g)
-                    tgt, acc = tmp, 0
-                else:
-                    tgt, acc = self.grad_of(s)
-                    if stride != 1:
-                        # parity classes only touch their own pixels: zero first, then accumulate
-                        if not acc:
-                            self.fill(self.bwd, tgt.buf, tgt.npix * tgt.ldc)
-                        acc = 1
-                relu_x = r.t if r.relu else None
-                for (py, px, sub), wT, k3 in zip(classes, packs, dg_s3):
-                    def shape_only(d, s=s, sub=sub, tgt=tgt, py=py, px=px, k3=k3):
-                        H, W = tgt.H, tgt.W
-                        d.N = dz.N
-                        d.OH, d.OW = (H, W) if stride == 1 else ((H - py + 1) // 2, (W - px + 1) // 2)
-                        d.Cout, d.nsrc = s.t.C, 1
-                        sv = d.src[0]
-                        sv.C, sv.ldc, sv.H, sv.W = Kd, dz.ldc, dz.H, dz.W
-                        d.ntaps = len(sub)
-                        for i, (dy, dx, _) in enumerate(sub):
-                            d.tdy[i], d.tdx[i] = dy, dx
-                        d.in_stride, d.gather = 1, gather
-                        d.out_sy = d.out_sx = stride
-                        d.splitk_ws, d.splitk_ws_bytes = 1, SPLITK_BYTES
-                        d.splitk_tickets = 1 if self.sk_fused else None
-                        d.w_s3 = 1 if k3 else None
-                    # filled in by the BatchNorm backward of the layer that produced this operand when THIS launch is
-                    # the last writer of its output gradient: the launch then also writes the BN-backward partial sums
-                    hook = {}
+        def shape_only(d):
+            self._dgrad_shape(d, dz, Kd, gather, sub, H, W, sum(chans), out_stride=1, w_s3=True, dst_C=chans)
+        # the library's own eligibility rule, on the shape-only descriptor (a mismatch would otherwise only surface as
+        # PMF_E_ARG when the plan runs) -- before grad_of, which allocates
+        probe = L.ConvDesc()
+        shape_only(probe)
+        if not L.lib().pmf_conv_multi_ok(C.byref(probe)):
+            return False
+        dsts = [(s,) + self.grad_of(s) + ({},) for s in srcs]       # (operand, gradient tensor, accumulate, BN-carry hook)
 
-                    def f(op, s=s, r=r, sub=sub, wT=wT, tgt=tgt, acc=acc, coloff=(0 if own_packs else coloff), py=py, px=px,
-                          relu_x=relu_x, shape_only=shape_only, hook=hook, k3=k3, ldwT=ldwT):
-                        d = op.u.conv
-                        shape_only(d)
-                        H, W = tgt.H, tgt.W
-                        d.src[0].x = dz.buf.ptr
-                        d.ldw = ldwT
-                        if k3:      # fragment column coloff / 32 (3 planes x 1 KiB each)
-                            d.w_s3 = wT.ptr + (coloff // 32) * 3 * 1024
-                        else:
-                            d.w = wT.at(coloff)
-                        d.act = L.ACT_NONE
-                        d.out, d.out_ldc, d.out_H, d.out_W = tgt.buf.ptr, tgt.ldc, H, W
-                        d.out_sy = d.out_sx = stride
-                        d.out_oy, d.out_ox = py, px
-                        d.accumulate = acc
-                        d.splitk_ws, d.splitk_ws_bytes = self.sk_bufs[lane].ptr, self.sk_bufs[lane].nbytes
-                        d.splitk_tickets = self.sk_tickets[lane].ptr if self.sk_fused else None
-                        if s.cmul is not None:
-                            d.ep_cmul, d.ep_cmul_ld = self.masks_ptr + 4 * s.cmul, s.cmul_ld
-                        if relu_x is not None:
-                            d.ep_relu_x, d.ep_relu_ldc = relu_x.buf.ptr, relu_x.ldc
-                            d.ep_relu_scale = r.scale.ptr if r.scale is not None else None
-                            d.ep_relu_shift = r.shift.ptr if r.shift is not None else None
-                        if hook:
-                            d.stats, d.ep_stat_mean = hook["rows"].ptr, hook["mean"].ptr
-                            if relu_x is None:
-                                d.ep_relu_x, d.ep_relu_ldc, d.ep_flags = r.t.buf.ptr, r.t.ldc, L.EP_STAT_X_ONLY
-                    self.emit(self.bwd, L.OP_CONV, f)
-                    if (stride == 1 and tmp is None and r.bn is not None and tgt is r.gy and self.bn_bwd_fused):
-                        r._gy_last = dict(hook=hook, index=len(self.bwd) - 1, shape=shape_only, lane=lane)
-                    mh = tgt.H if stride == 1 else (tgt.H - py + 1) // 2
-                    mw = tgt.W if stride == 1 else (tgt.W - px + 1) // 2
-                    self.meta_bwd[len(self.bwd) - 1] = dict(
-                        family="conv_dgrad", flops=2.0 * dz.N * mh * mw * s.t.C * Cout * len(sub), name=name,
-                        shape="%dx%dx%d %d->%d t%d s%d" % (dz.N, mh, mw, Cout, s.t.C, len(sub), stride))
-                if tmp is not None:
-                    crows = self.act.alloc(COL_ROWS * tmp.N * _ru(r.t.g.ldc, 4) * 4)
+        def f(op):
+            d = op.u.conv
+            shape_only(d)
+            d.src[0].x = dz.buf.ptr
+            d.ldw, d.w_s3, d.act = ldwT, wT.ptr, L.ACT_NONE
+            d.out_H, d.out_W = H, W
+            d.out, d.out_ldc = dsts[0][1].buf.ptr, dsts[0][1].ldc
+            for k, dst in enumerate(dsts):
+                self._dgrad_epilogue(d.dst[k], *dst)
+        self.emit(self.bwd, L.OP_CONV, f)
+        for s, tgt, _, hook in dsts:
+            self._arm_bn_carry(s.root(), tgt, hook, shape_only)
+        self.meta_bwd[len(self.bwd) - 1] = dict(
+            family="conv_dgrad", flops=2.0 * dz.N * H * W * sum(chans) * conv.out_channels * len(sub), name=name,
+            shape="%dx%dx%d %d->%s t%d s1" % (dz.N, H, W, conv.out_channels, "+".join(str(c) for c in chans), len(sub)))
+        return True
 
-                    def fc(op, tmp=tmp, g=r.t.g, crows=crows):
-                        a = op.u.sm
-                        a.p[0], a.p[1], a.p[2] = tmp.buf.ptr, g.buf.ptr, crows.ptr
-                        a.i[0], a.i[1], a.i[2] = tmp.ldc, g.ldc, tmp.N
-                        a.l[0] = tmp.H * tmp.W
-                    self.emit(self.bwd, L.OP_COLSUM, fc)
-            coloff += Cs
+    def _dgrad_operand(self, s, conv, dz, Kd, gather, stride, classes, dg_s3, packs, ldwT, coloff, name):
+        """the input-gradient launches of ONE operand, one per parity class; its columns of the transposed packs start at
+        ``coloff``"""
+        r = s.root()
+        if s.bcast:
+            # 1x1 map broadcast over the image: full-size gradient into a temp, then per-sample column sums
+            tmp = T(self, dz.N, dz.H, dz.W, s.t.C, name + ".bcast_tmp")
+            if r.t.g is None:
+                r.t.g = T(self, r.t.N, 1, 1, r.t.C, r.t.name + ".g", arena=self.zero_bwd, ldc=r.t.ldc)
+            r.t.g_written = True
+            self._touch(r.t.g)
+            tgt, acc = tmp, 0
+        else:
+            tgt, acc = self.grad_of(s)
+            if stride != 1:
+                # parity classes only touch their own pixels: zero first, then accumulate
+                if not acc:
+                    self.fill(self.bwd, tgt.buf, tgt.npix * tgt.ldc)
+                acc = 1
+        for cls, wT, k3 in zip(classes, packs, dg_s3):
+            self._dgrad_launch(s, tgt, acc, conv, dz, Kd, gather, stride, cls, wT, k3, ldwT, coloff, name)
+        if s.bcast:
+            g = r.t.g
+            crows = self.act.alloc(COL_ROWS * tmp.N * _ru(g.ldc, 4) * 4)
+            self.emit(self.bwd, L.OP_COLSUM, lambda op: _sm(
+                op, p=(tmp.buf.ptr, g.buf.ptr, crows.ptr), i=(tmp.ldc, g.ldc, tmp.N), l=(tmp.H * tmp.W,)))
 
+    def _dgrad_launch(self, s, tgt, acc, conv, dz, Kd, gather, stride, cls, wT, k3, ldwT, coloff, name):
+        """one input-gradient launch: parity class ``cls`` of the gradient of operand ``s`` into ``tgt``"""
+        (py, px, sub), lane, Cout = cls, self.lane, conv.out_channels
+        mh, mw = _class_hw(tgt.H, tgt.W, stride, py, px)
+
+        def shape_only(d):
+            self._dgrad_shape(d, dz, Kd, gather, sub, mh, mw, s.t.C, out_stride=stride, w_s3=bool(k3), splitk=True)
+        # filled in by the BatchNorm backward of the layer that produced this operand when THIS launch is the last
+        # writer of its output gradient: the launch then also writes the BN-backward partial sums (_arm_bn_carry)
+        hook = {}
+
+        def f(op):
+            d = op.u.conv
+            shape_only(d)
+            d.src[0].x = dz.buf.ptr
+            d.ldw = ldwT
+            if k3:      # fragment column coloff / 32 (3 planes x 1 KiB each)
+                d.w_s3 = wT.ptr + (coloff // 32) * 3 * 1024
+            else:
+                d.w = wT.at(coloff)
+            d.act = L.ACT_NONE
+            d.out_H, d.out_W = tgt.H, tgt.W
+            d.out_oy, d.out_ox = py, px
+            d.splitk_ws, d.splitk_ws_bytes = self.sk_bufs[lane].ptr, self.sk_bufs[lane].nbytes
+            d.splitk_tickets = self.sk_tickets[lane].ptr if self.sk_fused else None
+            self._dgrad_epilogue(d, s, tgt, acc, hook)
+        self.emit(self.bwd, L.OP_CONV, f)
+        if stride == 1:
+            self._arm_bn_carry(s.root(), tgt, hook, shape_only)
+        self.meta_bwd[len(self.bwd) - 1] = dict(
+            family="conv_dgrad", flops=2.0 * dz.N * mh * mw * s.t.C * Cout * len(sub), name=name,
+            shape="%dx%dx%d %d->%d t%d s%d" % (dz.N, mh, mw, Cout, s.t.C, len(sub), stride))
+
+    # ------------------------------------------------------------------ weight gradient
     def _wgrad(self, srcs, conv, dz, taps, stride, gather, name, dbias_rows=0, dbr=None, dbr_ld=0):
         Cout = conv.out_channels
         goff = self.pgrad(conv.weight)
@@ -618,7 +585,7 @@ class PlanConvMixin(object):
 
         def emit_ops():          # on the current lane
             if ws is not None:
-                def fb(op, f=f, ws=ws):
+                def fb(op):
                     f(op)
                     op.u.wgrad.partial = ws.ptr
                 self.emit(self.bwd, L.OP_WGRAD_PART, fb)
@@ -646,7 +613,7 @@ class PlanConvMixin(object):
             if len(q) >= self.wgrad_batch:
                 self.flush_wgrads(home)
 
-    def flush_wgrads(self, home, final=False):
+    def flush_wgrads(self, home):
         q = self._wg_deferred.pop(home, [])
         if not q:
             return
@@ -668,7 +635,7 @@ class PlanConvMixin(object):
             return
         prev, self.lane = self.lane, lane
 
-        def f(op, pend=pend):
+        def f(op):
             lib = L.lib()
             n = len(pend)
             descs = (L.WgradDesc * n)()
@@ -689,9 +656,7 @@ class PlanConvMixin(object):
             jd = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(self.device)
             md = torch.frombuffer(bytearray(bytes(meta)), dtype=torch.uint8).to(self.device)
             self._red_tables.append((jd, md))                  # keep the device tables alive with the plan
-            a = op.u.sm
-            a.p[0], a.p[1] = jd.data_ptr(), md.data_ptr()
-            a.i[0], a.i[1] = n, blocks
+            _sm(op, p=(jd.data_ptr(), md.data_ptr()), i=(n, blocks))
         self.emit(self.bwd, L.OP_WGRAD_RED_MULTI, f)
         # data parallelism: the gradients this launch finalises (and everything listed before it) may be all-reduced as
         # soon as it AND the ops emitted so far on the two home lanes have run -- one event each; the engine makes its RCCL
