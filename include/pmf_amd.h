@@ -338,7 +338,8 @@ int pmf_pmask_mul_bwd(const float* gy, int32_t gy_ldc, const float* mask, int64_
                       int32_t gx_ldc, int32_t acc, pmf_stream_t s);
 int pmf_vec_add(const float* a, const float* b, float* out, int32_t n, pmf_stream_t s);
 /* softmax over channels of NHWC logits -> NCHW probabilities (pmf_net.py:176-178,221) and gradient
- * dlogit[n,y,x,c] = p*(g - sum_k g_k p_k) from NCHW p, g. */
+ * dlogit[n,y,x,c] = p*(g - sum_k g_k p_k) from NCHW p, g.  C <= 32 (ldc <= 32 in the backward), else PMF_E_UNSUPPORTED;
+ * 33..64 channels: pmf_softmax_wide / pmf_softmax_wide_bwd of pmf_amd_wide.h. */
 int pmf_softmax_nhwc_to_nchw(const float* logits, int32_t ldc, int32_t N, int32_t HW, int32_t C, float* prob_nchw,
                              pmf_stream_t s);
 int pmf_softmax_bwd_nchw_to_nhwc(const float* prob_nchw, const float* g_nchw, int32_t N, int32_t HW, int32_t C,
@@ -504,6 +505,7 @@ int pmf_lovasz_grad(const float* fg_sorted, int32_t C, int64_t P, const int64_t*
  *   [2, 32], N < 1, HW < 1, a null pointer among the probabilities, label, alpha, cnt, the gradient maps, key, rows (w6;
  *   parts, dice), or ONE of conf_lidar / conf_camera null without the other: PMF_E_ARG.  Both null: no confusion matrices.
  *   More than 2^31 - 1 blocks of 256 pixels: PMF_E_UNSUPPORTED.
+ *   33..64 classes: pmf_loss_pixel_wide, pmf_loss_lovasz_sort_wide and pmf_loss_dice_finish_wide of pmf_amd_wide.h.
  * Where the stage is not the torch modules (pinned by tests/test_gpu_loss_pixel.py):
  *   - a batch without a labelled pixel: FocalSoftmaxLoss(..., mask) divides 0 by 0 and returns NaN; here foc = foc_cam = 0
  *     and the gradients are finite (the perception-aware terms alone);

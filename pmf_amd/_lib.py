@@ -3,7 +3,8 @@
 The header is the only place a constant, a struct member or a signature is written: read_header() turns its text into the
 PMF_* integers, the ctypes structs and the argtypes / restype of every prototype.  The reader is strict -- a declaration it
 cannot classify raises PMFLibraryError naming it, it never skips or guesses.  include/pmf_amd_sensat.h (the SensatUrban
-training loader) is a second header read the same way on top of the first: EXPORTS_SENSAT, BevSample.
+training loader) is a second header read the same way on top of the first: EXPORTS_SENSAT, BevSample.  include/pmf_amd_wide.h
+(33 to 64 classes in the heads and the fused objective) is a third: EXPORTS_WIDE.
 
 The product path has NO fallback: if the header or the shared library is missing, or the library's struct layout
 disagrees with the header, importing a compute entry point raises.
@@ -17,6 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpmf_amd.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "pmf_amd.h")
 SENSAT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "pmf_amd_sensat.h")
+WIDE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "pmf_amd_wide.h")
 
 
 class PMFLibraryError(RuntimeError):
@@ -207,6 +209,8 @@ def _read(path=None, struct_names=_STRUCT_NAMES, base=None):
 _H = _read()
 # the SensatUrban training loader's part of the ABI (csrc/bev_train.hip): a header of its own on top of the first one
 _HS = _read(SENSAT_HEADER_PATH, _SENSAT_STRUCT_NAMES, _H)
+# 33..64 classes (csrc/elementwise.hip, csrc/loss.hip): prototypes only, no struct and no constant
+_HW = _read(WIDE_HEADER_PATH, {}, _H)
 # PMF_ACT_RELU -> ACT_RELU, PMF_OP_CONV -> OP_CONV, PMF_MAX_SRC -> MAX_SRC ...; the error codes keep their prefix (PMF_E_ARG)
 globals().update((k if k.startswith("PMF_E_") else k[4:], v) for k, v in _H.consts.items() if k.startswith("PMF_"))
 globals().update((py, _H.structs[c]) for c, py in _STRUCT_NAMES.items())
@@ -216,12 +220,14 @@ EXPORTS = list(_H.protos)       # every function the header declares
 globals().update((k[4:], v) for k, v in _HS.consts.items() if k.startswith("PMF_"))      # BEV_HFLIP, BEV_VFLIP
 globals().update((py, _HS.structs[c]) for c, py in _SENSAT_STRUCT_NAMES.items())
 EXPORTS_SENSAT = list(_HS.protos)       # every function pmf_amd_sensat.h declares
+EXPORTS_WIDE = list(_HW.protos)         # every function pmf_amd_wide.h declares
+NARROW_CLASSES, WIDE_CLASSES = 32, 64   # class limit of pmf_amd.h's softmax / loss entry points, and of pmf_amd_wide.h's
 
 
 def bind(handle):
     """Set restype and argtypes of every function of the header that `handle` (a CDLL of this library, or of a private
     build of some of its sources) exports; returns the handle."""
-    for name, (restype, argtypes) in list(_H.protos.items()) + list(_HS.protos.items()):
+    for name, (restype, argtypes) in list(_H.protos.items()) + list(_HS.protos.items()) + list(_HW.protos.items()):
         fn = getattr(handle, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes
@@ -247,6 +253,12 @@ def lib():
     missing = [name for name in EXPORTS_SENSAT if not hasattr(L, name)]
     if missing:
         raise PMFLibraryError("pmf_amd: %s lacks %s, which include/pmf_amd_sensat.h declares" % (LIB_PATH, ", ".join(missing)))
+    missing = [name for name in EXPORTS_WIDE if not hasattr(L, name)]
+    if missing:
+        raise PMFLibraryError("pmf_amd: %s lacks %s, which include/pmf_amd_wide.h declares" % (LIB_PATH, ", ".join(missing)))
+    if L.pmf_wide_max_classes() != WIDE_CLASSES:
+        raise PMFLibraryError("pmf_amd: %s takes up to %d classes, the binding expects %d"
+                              % (LIB_PATH, L.pmf_wide_max_classes(), WIDE_CLASSES))
     for which, st in enumerate((Src, ConvDesc, WgradDesc, View, SmallArgs, Op, PackJob)):    # the order pmf_sizeof documents
         if L.pmf_sizeof(which) != C.sizeof(st):
             raise PMFLibraryError("pmf_amd ABI mismatch for %s: lib %d vs binding %d"

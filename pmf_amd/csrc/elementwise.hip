@@ -2,6 +2,7 @@
 // fusion gate, channel softmax, layout change, column reductions.  All NHWC fp32, one float4 (4 channels) per
 // lane so a wavefront moves 1 KiB per instruction; "views" fold BatchNorm-apply / ReLU / Dropout2d into the load.
 #include "common.h"
+#include "../../include/pmf_amd_wide.h"
 
 #define EW_BLOCK 256
 static inline int ew_grid(int64_t items) {
@@ -640,78 +641,87 @@ extern "C" int pmf_fusion_gate_bwd(const float* gout, int32_t g_ldc, const pmf_v
 
 // ------------------------------------------------------------------ channel softmax, NHWC logits <-> NCHW probabilities
 #define SM_MAXC 32
+#define SM_WIDE_MAXC 64
 // VEC: the NHWC side moves as 16-byte vectors (ldc a multiple of 4, base 16-byte aligned): a thread owns one pixel, so a
 // scalar access per channel touches as many cache lines per instruction as a vector access that moves four channels
 // IDENT: no softmax, the logits themselves go out (SalsaNext(softmax=False), salsanext.py:167,206-207)
-template <bool VEC, bool IDENT = false>
-__global__ void softmax_k(const float* __restrict__ lg, int ldc, int N, int HW, int C, float* __restrict__ prob) {
+// MAXC: the capacity the pixel's row in registers is unrolled over.  32 is what pmf_amd.h's entry points launch, under the
+// default launch bound (1024 threads, 128 VGPRs).  64 (33..64 classes, pmf_amd_wide.h) is the same body under a bound of
+// EW_BLOCK threads: a 64-float row (two of them in the backward) does not fit next to the addressing in 128 VGPRs -- it
+// spills 80..100 bytes per lane -- and does in the 512 a 256-thread workgroup may use.  Same float32 operations, same order.
+#define SM_THREADS(MAXC) ((MAXC) > SM_MAXC ? EW_BLOCK : 1024)
+template <int MAXC, bool VEC, bool IDENT = false>
+__global__ __launch_bounds__(SM_THREADS(MAXC)) void softmax_k(const float* __restrict__ lg, int ldc, int N, int HW, int C, float* __restrict__ prob) {
   const int64_t total = (int64_t)N * HW;
   for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < total; p += (int64_t)gridDim.x * blockDim.x) {
     const int n = (int)(p / HW);
     const int64_t hw = p - (int64_t)n * HW;
-    float v[SM_MAXC];
+    float v[MAXC];
     if (VEC) {
 #pragma unroll
-      for (int q = 0; q < SM_MAXC / 4; ++q)
+      for (int q = 0; q < MAXC / 4; ++q)
         if (q * 4 < C) {
           const f32x4 t = *(const f32x4*)(lg + p * ldc + q * 4);
           v[q * 4] = t.x; v[q * 4 + 1] = t.y; v[q * 4 + 2] = t.z; v[q * 4 + 3] = t.w;
         }
     } else {
 #pragma unroll
-      for (int c = 0; c < SM_MAXC; ++c)
+      for (int c = 0; c < MAXC; ++c)
         if (c < C) v[c] = lg[p * ldc + c];
     }
     float inv = 1.f;
     if (!IDENT) {
       float m = -INFINITY;
 #pragma unroll
-      for (int c = 0; c < SM_MAXC; ++c)
+      for (int c = 0; c < MAXC; ++c)
         if (c < C) m = fmaxf(m, v[c]);
       float sum = 0.f;
 #pragma unroll
-      for (int c = 0; c < SM_MAXC; ++c)
+      for (int c = 0; c < MAXC; ++c)
         if (c < C) { v[c] = expf(v[c] - m); sum += v[c]; }
       inv = 1.f / sum;
     }
 #pragma unroll
-    for (int c = 0; c < SM_MAXC; ++c)
+    for (int c = 0; c < MAXC; ++c)
       if (c < C) prob[((int64_t)n * C + c) * HW + hw] = v[c] * inv;
   }
+}
+static inline bool softmax_vec(const float* logits, int32_t ldc, int32_t C) {
+  return (ldc & 3) == 0 && ((uintptr_t)logits & 15) == 0 && ((C + 3) & ~3) <= ldc;
 }
 extern "C" int pmf_softmax_nhwc_to_nchw(const float* logits, int32_t ldc, int32_t N, int32_t HW, int32_t C,
                                         float* prob_nchw, pmf_stream_t s) {
   if (C > SM_MAXC || C < 1) return PMF_E_UNSUPPORTED;
-  const bool vec = (ldc & 3) == 0 && ((uintptr_t)logits & 15) == 0 && ((C + 3) & ~3) <= ldc;
-  if (vec) hipLaunchKernelGGL(softmax_k<true>, dim3(ew_grid((int64_t)N * HW)), dim3(EW_BLOCK), 0, (hipStream_t)s, logits, ldc,
-                              N, HW, C, prob_nchw);
-  else hipLaunchKernelGGL(softmax_k<false>, dim3(ew_grid((int64_t)N * HW)), dim3(EW_BLOCK), 0, (hipStream_t)s, logits, ldc, N,
-                          HW, C, prob_nchw);
+  const bool vec = softmax_vec(logits, ldc, C);
+  if (vec) hipLaunchKernelGGL((softmax_k<SM_MAXC, true>), dim3(ew_grid((int64_t)N * HW)), dim3(EW_BLOCK), 0, (hipStream_t)s,
+                              logits, ldc, N, HW, C, prob_nchw);
+  else hipLaunchKernelGGL((softmax_k<SM_MAXC, false>), dim3(ew_grid((int64_t)N * HW)), dim3(EW_BLOCK), 0, (hipStream_t)s, logits,
+                          ldc, N, HW, C, prob_nchw);
   PMF_LAUNCH_CHECK();
   return 0;
 }
 extern "C" int pmf_logits_nhwc_to_nchw(const float* logits, int32_t ldc, int32_t N, int32_t HW, int32_t C, float* out_nchw,
                                        pmf_stream_t s) {
   if (C > SM_MAXC || C < 1) return PMF_E_UNSUPPORTED;
-  const bool vec = (ldc & 3) == 0 && ((uintptr_t)logits & 15) == 0 && ((C + 3) & ~3) <= ldc;
-  if (vec) hipLaunchKernelGGL((softmax_k<true, true>), dim3(ew_grid((int64_t)N * HW)), dim3(EW_BLOCK), 0, (hipStream_t)s,
+  const bool vec = softmax_vec(logits, ldc, C);
+  if (vec) hipLaunchKernelGGL((softmax_k<SM_MAXC, true, true>), dim3(ew_grid((int64_t)N * HW)), dim3(EW_BLOCK), 0, (hipStream_t)s,
                               logits, ldc, N, HW, C, out_nchw);
-  else hipLaunchKernelGGL((softmax_k<false, true>), dim3(ew_grid((int64_t)N * HW)), dim3(EW_BLOCK), 0, (hipStream_t)s, logits,
-                          ldc, N, HW, C, out_nchw);
+  else hipLaunchKernelGGL((softmax_k<SM_MAXC, false, true>), dim3(ew_grid((int64_t)N * HW)), dim3(EW_BLOCK), 0, (hipStream_t)s,
+                          logits, ldc, N, HW, C, out_nchw);
   PMF_LAUNCH_CHECK();
   return 0;
 }
-template <bool VEC, bool IDENT = false>
-__global__ void softmax_bwd_k(const float* __restrict__ prob, const float* __restrict__ g, int N, int HW, int C,
+template <int MAXC, bool VEC, bool IDENT = false>
+__global__ __launch_bounds__(SM_THREADS(MAXC)) void softmax_bwd_k(const float* __restrict__ prob, const float* __restrict__ g, int N, int HW, int C,
                               float* __restrict__ dl, int ldc) {
   const int64_t total = (int64_t)N * HW;
   for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < total; p += (int64_t)gridDim.x * blockDim.x) {
     const int n = (int)(p / HW);
     const int64_t hw = p - (int64_t)n * HW;
-    float pv[SM_MAXC], gv[SM_MAXC];
+    float pv[MAXC], gv[MAXC];
     float dot = 0.f;
 #pragma unroll
-    for (int c = 0; c < SM_MAXC; ++c)
+    for (int c = 0; c < MAXC; ++c)
       if (c < C) {
         pv[c] = IDENT ? 1.f : prob[((int64_t)n * C + c) * HW + hw];
         gv[c] = g[((int64_t)n * C + c) * HW + hw];
@@ -719,7 +729,7 @@ __global__ void softmax_bwd_k(const float* __restrict__ prob, const float* __res
       }
     if (VEC) {
 #pragma unroll
-      for (int q = 0; q < SM_MAXC / 4; ++q)
+      for (int q = 0; q < MAXC / 4; ++q)
         if (q * 4 < ldc) {
           f32x4 t;
           t.x = q * 4 + 0 < C ? pv[q * 4 + 0] * (gv[q * 4 + 0] - dot) : 0.f;
@@ -730,7 +740,7 @@ __global__ void softmax_bwd_k(const float* __restrict__ prob, const float* __res
         }
     } else {
 #pragma unroll
-      for (int c = 0; c < SM_MAXC; ++c)
+      for (int c = 0; c < MAXC; ++c)
         if (c < ldc) dl[p * ldc + c] = c < C ? pv[c] * (gv[c] - dot) : 0.f;
     }
   }
@@ -739,10 +749,10 @@ extern "C" int pmf_softmax_bwd_nchw_to_nhwc(const float* prob_nchw, const float*
                                             int32_t C, float* dlogits, int32_t ldc, pmf_stream_t s) {
   if (C > SM_MAXC || ldc > SM_MAXC) return PMF_E_UNSUPPORTED;
   const bool vec = (ldc & 3) == 0 && ((uintptr_t)dlogits & 15) == 0;
-  if (vec) hipLaunchKernelGGL(softmax_bwd_k<true>, dim3(ew_grid((int64_t)N * HW)), dim3(EW_BLOCK), 0, (hipStream_t)s, prob_nchw,
-                              g_nchw, N, HW, C, dlogits, ldc);
-  else hipLaunchKernelGGL(softmax_bwd_k<false>, dim3(ew_grid((int64_t)N * HW)), dim3(EW_BLOCK), 0, (hipStream_t)s, prob_nchw,
-                          g_nchw, N, HW, C, dlogits, ldc);
+  if (vec) hipLaunchKernelGGL((softmax_bwd_k<SM_MAXC, true>), dim3(ew_grid((int64_t)N * HW)), dim3(EW_BLOCK), 0, (hipStream_t)s,
+                              prob_nchw, g_nchw, N, HW, C, dlogits, ldc);
+  else hipLaunchKernelGGL((softmax_bwd_k<SM_MAXC, false>), dim3(ew_grid((int64_t)N * HW)), dim3(EW_BLOCK), 0, (hipStream_t)s,
+                          prob_nchw, g_nchw, N, HW, C, dlogits, ldc);
   PMF_LAUNCH_CHECK();
   return 0;
 }
@@ -751,10 +761,54 @@ extern "C" int pmf_logits_bwd_nchw_to_nhwc(const float* g_nchw, int32_t N, int32
                                            pmf_stream_t s) {
   if (C > SM_MAXC || ldc > SM_MAXC) return PMF_E_UNSUPPORTED;
   const bool vec = (ldc & 3) == 0 && ((uintptr_t)dlogits & 15) == 0;
-  if (vec) hipLaunchKernelGGL((softmax_bwd_k<true, true>), dim3(ew_grid((int64_t)N * HW)), dim3(EW_BLOCK), 0, (hipStream_t)s,
-                              nullptr, g_nchw, N, HW, C, dlogits, ldc);
-  else hipLaunchKernelGGL((softmax_bwd_k<false, true>), dim3(ew_grid((int64_t)N * HW)), dim3(EW_BLOCK), 0, (hipStream_t)s,
-                          nullptr, g_nchw, N, HW, C, dlogits, ldc);
+  if (vec) hipLaunchKernelGGL((softmax_bwd_k<SM_MAXC, true, true>), dim3(ew_grid((int64_t)N * HW)), dim3(EW_BLOCK), 0,
+                              (hipStream_t)s, nullptr, g_nchw, N, HW, C, dlogits, ldc);
+  else hipLaunchKernelGGL((softmax_bwd_k<SM_MAXC, false, true>), dim3(ew_grid((int64_t)N * HW)), dim3(EW_BLOCK), 0,
+                          (hipStream_t)s, nullptr, g_nchw, N, HW, C, dlogits, ldc);
+  PMF_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- 33..64 classes (include/pmf_amd_wide.h).  C <= 32 goes to the entry points above, i.e. to the very <32> kernels; the
+// <64> kernels are launched with one thread per pixel and no grid cap (their grid-stride loop runs once).
+extern "C" int pmf_wide_max_classes(void) { return SM_WIDE_MAXC; }
+
+extern "C" int pmf_softmax_wide(const float* logits, int32_t ldc, int32_t N, int32_t HW, int32_t C, int32_t ident,
+                                float* out_nchw, pmf_stream_t s) {
+  if (C > SM_WIDE_MAXC || C < 1) return PMF_E_UNSUPPORTED;
+  if (C <= SM_MAXC)
+    return ident ? pmf_logits_nhwc_to_nchw(logits, ldc, N, HW, C, out_nchw, s)
+                 : pmf_softmax_nhwc_to_nchw(logits, ldc, N, HW, C, out_nchw, s);
+  const int64_t nblk = cdiv64((int64_t)N * HW, EW_BLOCK);
+  if (nblk > 0x7fffffffll) return PMF_E_UNSUPPORTED;
+  if (nblk < 1) return 0;
+  const bool vec = softmax_vec(logits, ldc, C);
+  const dim3 grid((unsigned)nblk), blk(EW_BLOCK);
+  hipStream_t st = (hipStream_t)s;
+  if (vec && ident) hipLaunchKernelGGL((softmax_k<SM_WIDE_MAXC, true, true>), grid, blk, 0, st, logits, ldc, N, HW, C, out_nchw);
+  else if (vec) hipLaunchKernelGGL((softmax_k<SM_WIDE_MAXC, true, false>), grid, blk, 0, st, logits, ldc, N, HW, C, out_nchw);
+  else if (ident) hipLaunchKernelGGL((softmax_k<SM_WIDE_MAXC, false, true>), grid, blk, 0, st, logits, ldc, N, HW, C, out_nchw);
+  else hipLaunchKernelGGL((softmax_k<SM_WIDE_MAXC, false, false>), grid, blk, 0, st, logits, ldc, N, HW, C, out_nchw);
+  PMF_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int pmf_softmax_wide_bwd(const float* prob_nchw, const float* g_nchw, int32_t N, int32_t HW, int32_t C,
+                                    int32_t ident, float* dlogits, int32_t ldc, pmf_stream_t s) {
+  if (C > SM_WIDE_MAXC || ldc > SM_WIDE_MAXC) return PMF_E_UNSUPPORTED;
+  if (C <= SM_MAXC && ldc <= SM_MAXC)
+    return ident ? pmf_logits_bwd_nchw_to_nhwc(g_nchw, N, HW, C, dlogits, ldc, s)
+                 : pmf_softmax_bwd_nchw_to_nhwc(prob_nchw, g_nchw, N, HW, C, dlogits, ldc, s);
+  const int64_t nblk = cdiv64((int64_t)N * HW, EW_BLOCK);
+  if (nblk > 0x7fffffffll) return PMF_E_UNSUPPORTED;
+  if (nblk < 1) return 0;
+  const bool vec = (ldc & 3) == 0 && ((uintptr_t)dlogits & 15) == 0;
+  const dim3 grid((unsigned)nblk), blk(EW_BLOCK);
+  hipStream_t st = (hipStream_t)s;
+  if (vec && ident) hipLaunchKernelGGL((softmax_bwd_k<SM_WIDE_MAXC, true, true>), grid, blk, 0, st, (const float*)nullptr, g_nchw, N, HW, C, dlogits, ldc);
+  else if (vec) hipLaunchKernelGGL((softmax_bwd_k<SM_WIDE_MAXC, true, false>), grid, blk, 0, st, prob_nchw, g_nchw, N, HW, C, dlogits, ldc);
+  else if (ident) hipLaunchKernelGGL((softmax_bwd_k<SM_WIDE_MAXC, false, true>), grid, blk, 0, st, (const float*)nullptr, g_nchw, N, HW, C, dlogits, ldc);
+  else hipLaunchKernelGGL((softmax_bwd_k<SM_WIDE_MAXC, false, false>), grid, blk, 0, st, prob_nchw, g_nchw, N, HW, C, dlogits, ldc);
   PMF_LAUNCH_CHECK();
   return 0;
 }

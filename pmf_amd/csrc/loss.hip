@@ -5,6 +5,7 @@
 // the innermost dimension cost 0.57 ms per [20, 262144] call (4 calls per iteration); this is HBM-bound at
 // 8 B per element.  Only the first n_valid positions of a row are real (ignored pixels were sorted to the tail).
 #include "common.h"
+#include "../../include/pmf_amd_wide.h"
 
 #define LV_BLOCK 256
 #define LV_PER_THREAD 16
@@ -130,11 +131,15 @@ extern "C" int pmf_lovasz_grad(const float* fg_sorted, int32_t C, int64_t P, con
 //   focal: f = -(1-pt)^g ln max(pt,1e-6) alpha_t,  df/dpt = alpha_t (g (1-pt)^(g-1) ln max(pt,1e-6) - (1-pt)^g [pt>=1e-6]/pt)
 #define LP_BLOCK 256
 #define LP_MAXC 32
+// 33..64 classes (include/pmf_amd_wide.h): the kernels that size something by the class capacity take it as the template
+// parameter MAXC; <LP_MAXC> is what the entry points of pmf_amd.h launch, <LP_WIDE_MAXC> only ever runs for C > LP_MAXC
+#define LP_WIDE_MAXC 64
 
+template <int MAXC>
 __global__ __launch_bounds__(256) void loss_count_k(const int64_t* __restrict__ label, int64_t P, int C,
                                                     unsigned long long* __restrict__ cnt) {
-  __shared__ unsigned int h[LP_MAXC];
-  if (threadIdx.x < LP_MAXC) h[threadIdx.x] = 0u;
+  __shared__ unsigned int h[MAXC];
+  if (threadIdx.x < MAXC) h[threadIdx.x] = 0u;
   __syncthreads();
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (int64_t)gridDim.x * blockDim.x) {
     const int t = (int)label[i];
@@ -162,10 +167,14 @@ struct LossPixelArgs {
 
 // DICE: add the exp-log Dice gradient of both heads (a.dice, see loss_dice_fold_k) at labelled pixels; the <false>
 // instantiation is the kernel as it was before the Dice term existed
-template <bool DICE>
+// MAXC <= LP_MAXC keeps the pixel's two probability rows in registers between the class loops.  The wide form does not --
+// p[64] and q[64] would live in 528 bytes of scratch per lane -- it reads p_c, q_c again in the second loop (the first loop
+// left them in cache) and fetches p[t], q[t] by index; the float32 operations and their order are the same.
+template <int MAXC, bool DICE>
 __global__ __launch_bounds__(LP_BLOCK) void loss_pixel_k(const LossPixelArgs a) {
+  constexpr bool KEEP = MAXC <= LP_MAXC;
   __shared__ double red[4][LP_BLOCK];
-  __shared__ unsigned int hist[2][LP_MAXC * LP_MAXC];
+  __shared__ unsigned int hist[2][MAXC * MAXC];
   const int C = a.C;
   const bool want_conf = a.conf_l != nullptr;
   if (want_conf) {
@@ -180,14 +189,14 @@ __global__ __launch_bounds__(LP_BLOCK) void loss_pixel_k(const LossPixelArgs a) 
     const float* pc = a.pc + n * C * a.HW + hw;
     const int t = (int)a.label[i];
     const float logC = logf((float)C), ilogC = 1.f / logC;
-    float p[LP_MAXC], q[LP_MAXC];
+    float p[KEEP ? MAXC : 1], q[KEEP ? MAXC : 1];
     float ep = 0.f, eq = 0.f, Lp = 0.f, Lq = 0.f;
     int am_l = 0, am_c = 0;
     float mx_l = -1.f, mx_c = -1.f;
 #pragma unroll 4
     for (int c = 0; c < C; ++c) {
       const float pv = pl[c * a.HW], qv = pc[c * a.HW];
-      p[c] = pv; q[c] = qv;
+      if constexpr (KEEP) { p[c] = pv; q[c] = qv; }
       const float plog = logf(fmaxf(pv, 1e-8f)), qlog = logf(fmaxf(qv, 1e-8f));
       ep -= pv * plog; eq -= qv * qlog;
       Lp += (qv > 0.f ? qv * logf(qv) : 0.f) - qv * plog;     // F.kl_div(plog, q): xlogy(q,q) - q*plog
@@ -214,7 +223,7 @@ __global__ __launch_bounds__(LP_BLOCK) void loss_pixel_k(const LossPixelArgs a) 
     float dfl = 0.f, dfc = 0.f;
     if (valid) {
       const float al = a.alpha[t];
-      const float ptl = p[t], ptc = q[t];
+      const float ptl = KEEP ? p[t] : pl[t * a.HW], ptc = KEEP ? q[t] : pc[t * a.HW];
       const float ll = logf(fmaxf(ptl, 1e-6f)), lc = logf(fmaxf(ptc, 1e-6f));
       const float ol = 1.f - ptl, oc = 1.f - ptc;
       const float pwl = powf(ol, a.fgamma), pwc = powf(oc, a.fgamma);
@@ -233,7 +242,7 @@ __global__ __launch_bounds__(LP_BLOCK) void loss_pixel_k(const LossPixelArgs a) 
     const float kd_l = DICE && valid ? (float)dl[1] : 0.f, kd_c = DICE && valid ? (float)dq[1] : 0.f;
 #pragma unroll 4
     for (int c = 0; c < C; ++c) {
-      const float pv = p[c], qv = q[c];
+      const float pv = KEEP ? p[c] : pl[c * a.HW], qv = KEEP ? q[c] : pc[c * a.HW];
       const float plog = logf(fmaxf(pv, 1e-8f)), qlog = logf(fmaxf(qv, 1e-8f));
       const float ip = pv >= 1e-8f ? 1.f : 0.f, iq = qv >= 1e-8f ? 1.f : 0.f;
       const float ddp = (plog + ip) * ilogC;       // dd/dp_c
@@ -478,11 +487,20 @@ __global__ __launch_bounds__(256) void loss_fold_k(const double* __restrict__ ro
 extern "C" int pmf_loss_rows(int64_t P) { return (int)cdiv64(P, LP_BLOCK); }
 extern "C" int pmf_loss_chunks(int64_t P) { return (int)cdiv64(P, LV_CHUNK); }
 
-static int loss_pixel_impl(const float* lidar_prob, const float* camera_prob, const int64_t* label, const float* alpha,
+// histogram + per-pixel kernel at capacity MAXC, after the guards
+template <int MAXC>
+static void loss_pixel_launch(const LossPixelArgs& a, hipStream_t st) {
+  int gb = (int)cdiv64(a.P, 256 * 8);
+  hipLaunchKernelGGL(loss_count_k<MAXC>, dim3(gb > 1024 ? 1024 : gb), dim3(256), 0, st, a.label, a.P, a.C,
+                     (unsigned long long*)a.cnt);
+  hipLaunchKernelGGL((loss_pixel_k<MAXC, false>), dim3((unsigned)cdiv64(a.P, LP_BLOCK)), dim3(LP_BLOCK), 0, st, a);
+}
+// maxc: LP_MAXC for the entry points of pmf_amd.h, LP_WIDE_MAXC for pmf_amd_wide.h's
+static int loss_pixel_impl(int maxc, const float* lidar_prob, const float* camera_prob, const int64_t* label, const float* alpha,
                            int32_t N, int32_t C, int64_t HW, float focal_gamma, float tau, float gamma_per,
                            const float* w6, unsigned long long* cnt, float* grad_lidar, float* grad_camera, float* key,
                            double* rows, unsigned long long* conf_lidar, unsigned long long* conf_camera, pmf_stream_t s) {
-  if (C < 2 || C > LP_MAXC || N < 1 || HW < 1) return PMF_E_ARG;
+  if (C < 2 || C > maxc || N < 1 || HW < 1) return PMF_E_ARG;
   if (!lidar_prob || !camera_prob || !label || !alpha || !cnt || !grad_lidar || !grad_camera || !key || !rows ||
       (conf_lidar == nullptr) != (conf_camera == nullptr))      // (the kernel tests conf_lidar alone and writes both)
     return PMF_E_ARG;
@@ -491,13 +509,12 @@ static int loss_pixel_impl(const float* lidar_prob, const float* camera_prob, co
   hipStream_t st = (hipStream_t)s;
   hipError_t e = hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * C, st);
   if (e != hipSuccess) return (int)e;
-  int gb = (int)cdiv64(P, 256 * 8);
-  hipLaunchKernelGGL(loss_count_k, dim3(gb > 1024 ? 1024 : gb), dim3(256), 0, st, label, P, C, cnt);
   LossPixelArgs a;
   a.pl = lidar_prob; a.pc = camera_prob; a.label = label; a.alpha = alpha; a.cnt = cnt;
   a.gl = grad_lidar; a.gc = grad_camera; a.key = key; a.rows = rows; a.conf_l = conf_lidar; a.conf_c = conf_camera;
   a.HW = HW; a.P = P; a.C = C; a.fgamma = focal_gamma; a.tau = tau; a.gamma_per = gamma_per; a.w6 = w6; a.dice = nullptr;
-  hipLaunchKernelGGL(loss_pixel_k<false>, dim3((unsigned)cdiv64(P, LP_BLOCK)), dim3(LP_BLOCK), 0, st, a);
+  if (C <= LP_MAXC) loss_pixel_launch<LP_MAXC>(a, st);
+  else loss_pixel_launch<LP_WIDE_MAXC>(a, st);
   PMF_LAUNCH_CHECK();
   return 0;
 }
@@ -505,7 +522,7 @@ extern "C" int pmf_loss_pixel(const float* lidar_prob, const float* camera_prob,
                               int32_t N, int32_t C, int64_t HW, float focal_gamma, float tau, float gamma_per,
                               unsigned long long* cnt, float* grad_lidar, float* grad_camera, float* key, double* rows,
                               unsigned long long* conf_lidar, unsigned long long* conf_camera, pmf_stream_t s) {
-  return loss_pixel_impl(lidar_prob, camera_prob, label, alpha, N, C, HW, focal_gamma, tau, gamma_per, nullptr, cnt,
+  return loss_pixel_impl(LP_MAXC, lidar_prob, camera_prob, label, alpha, N, C, HW, focal_gamma, tau, gamma_per, nullptr, cnt,
                          grad_lidar, grad_camera, key, rows, conf_lidar, conf_camera, s);
 }
 extern "C" int pmf_loss_pixel_w(const float* lidar_prob, const float* camera_prob, const int64_t* label, const float* alpha,
@@ -513,7 +530,7 @@ extern "C" int pmf_loss_pixel_w(const float* lidar_prob, const float* camera_pro
                                 unsigned long long* cnt, float* grad_lidar, float* grad_camera, float* key, double* rows,
                                 unsigned long long* conf_lidar, unsigned long long* conf_camera, pmf_stream_t s) {
   if (!w6) return PMF_E_ARG;
-  return loss_pixel_impl(lidar_prob, camera_prob, label, alpha, N, C, HW, focal_gamma, tau, 0.f, w6, cnt, grad_lidar,
+  return loss_pixel_impl(LP_MAXC, lidar_prob, camera_prob, label, alpha, N, C, HW, focal_gamma, tau, 0.f, w6, cnt, grad_lidar,
                          grad_camera, key, rows, conf_lidar, conf_camera, s);
 }
 
@@ -533,12 +550,13 @@ static_assert(DS_PER % 4 == 0, "loss_dice_sums_k: wave w counts the labels of ro
 // one workgroup = DS_TILE consecutive pixels; every wave reads the tile's labels (DS_PER per lane) and owns the classes
 // c = wave, wave + 4, ...: per class the lanes sum their pixels in float64, a wave reduction gives the tile's S_c and I_c of
 // both heads -> parts[tile][head][2C] (S at c, I at C + c).  The label histogram (loss_count_k's) is built on the way.
+template <int MAXC>
 __global__ __launch_bounds__(256) void loss_dice_sums_k(const float* __restrict__ pl, const float* __restrict__ pc,
                                                         const int64_t* __restrict__ label, int64_t HW, int64_t P, int C,
                                                         unsigned long long* __restrict__ cnt, double* __restrict__ parts) {
-  __shared__ unsigned int h[LP_MAXC];
+  __shared__ unsigned int h[MAXC];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x < LP_MAXC) h[threadIdx.x] = 0u;
+  if (threadIdx.x < MAXC) h[threadIdx.x] = 0u;
   __syncthreads();
   const int64_t base = (int64_t)blockIdx.x * DS_TILE;
   int t[DS_PER];
@@ -579,12 +597,13 @@ __global__ __launch_bounds__(256) void loss_dice_sums_k(const float* __restrict_
 // single workgroup, fixed summation order: parts[nparts][4C] -> dice[2][2 + 2C] = per head {L, K/C, dice_c[C], 1/D_c[C]}
 // (DF_GROUPS waves take every DF_GROUPS-th tile each, eight independent loads per trip; the group sums are added in group order)
 #define DF_GROUPS 16
+template <int MAXC>
 __global__ __launch_bounds__(64 * DF_GROUPS) void loss_dice_fold_k(const double* __restrict__ parts, int nparts, int C,
                                                                    const unsigned long long* __restrict__ cnt,
                                                                    double* __restrict__ dice) {
-  __shared__ double sh[DF_GROUPS][4 * LP_MAXC];
-  __shared__ double tot[4 * LP_MAXC];
-  __shared__ double dsh[2][LP_MAXC];
+  __shared__ double sh[DF_GROUPS][4 * MAXC];
+  __shared__ double tot[4 * MAXC];
+  __shared__ double dsh[2][MAXC];
   const int W = 4 * C, g = threadIdx.x >> 6;
   for (int col = threadIdx.x & 63; col < W; col += 64) {
     double a = 0.0;
@@ -640,12 +659,22 @@ __global__ void loss_dice_finish_k(const double* __restrict__ dice, int C, float
 
 extern "C" int pmf_loss_dice_parts(int64_t P) { return (int)cdiv64(P, DS_TILE); }
 
-extern "C" int pmf_loss_pixel_dice(const float* lidar_prob, const float* camera_prob, const int64_t* label, const float* alpha,
-                                   int32_t N, int32_t C, int64_t HW, float focal_gamma, float tau, float gamma_per,
-                                   unsigned long long* cnt, float* grad_lidar, float* grad_camera, float* key, double* rows,
-                                   unsigned long long* conf_lidar, unsigned long long* conf_camera, double* parts,
-                                   double* dice, pmf_stream_t s) {
-  if (C < 2 || C > LP_MAXC || N < 1 || HW < 1) return PMF_E_ARG;
+// class sums + fold + per-pixel kernel with the Dice gradient at capacity MAXC, after the guards
+template <int MAXC>
+static void loss_pixel_dice_launch(const LossPixelArgs& a, double* parts, double* dice, hipStream_t st) {
+  const int nparts = (int)cdiv64(a.P, DS_TILE);
+  hipLaunchKernelGGL(loss_dice_sums_k<MAXC>, dim3((unsigned)nparts), dim3(256), 0, st, a.pl, a.pc, a.label, a.HW, a.P, a.C,
+                     (unsigned long long*)a.cnt, parts);
+  hipLaunchKernelGGL(loss_dice_fold_k<MAXC>, dim3(1), dim3(64 * DF_GROUPS), 0, st, (const double*)parts, nparts, a.C, a.cnt,
+                     dice);
+  hipLaunchKernelGGL((loss_pixel_k<MAXC, true>), dim3((unsigned)cdiv64(a.P, LP_BLOCK)), dim3(LP_BLOCK), 0, st, a);
+}
+static int loss_pixel_dice_impl(int maxc, const float* lidar_prob, const float* camera_prob, const int64_t* label,
+                                const float* alpha, int32_t N, int32_t C, int64_t HW, float focal_gamma, float tau,
+                                float gamma_per, unsigned long long* cnt, float* grad_lidar, float* grad_camera, float* key,
+                                double* rows, unsigned long long* conf_lidar, unsigned long long* conf_camera, double* parts,
+                                double* dice, pmf_stream_t s) {
+  if (C < 2 || C > maxc || N < 1 || HW < 1) return PMF_E_ARG;
   if (!lidar_prob || !camera_prob || !label || !alpha || !cnt || !grad_lidar || !grad_camera || !key || !rows || !parts ||
       !dice || (conf_lidar == nullptr) != (conf_camera == nullptr))
     return PMF_E_ARG;
@@ -654,25 +683,32 @@ extern "C" int pmf_loss_pixel_dice(const float* lidar_prob, const float* camera_
   hipStream_t st = (hipStream_t)s;
   hipError_t e = hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * C, st);
   if (e != hipSuccess) return (int)e;
-  const int nparts = (int)cdiv64(P, DS_TILE);
-  hipLaunchKernelGGL(loss_dice_sums_k, dim3((unsigned)nparts), dim3(256), 0, st, lidar_prob, camera_prob, label, HW, P, (int)C,
-                     cnt, parts);
-  hipLaunchKernelGGL(loss_dice_fold_k, dim3(1), dim3(64 * DF_GROUPS), 0, st, (const double*)parts, nparts, (int)C,
-                     (const unsigned long long*)cnt, dice);
   LossPixelArgs a;
   a.pl = lidar_prob; a.pc = camera_prob; a.label = label; a.alpha = alpha; a.cnt = cnt;
   a.gl = grad_lidar; a.gc = grad_camera; a.key = key; a.rows = rows; a.conf_l = conf_lidar; a.conf_c = conf_camera;
   a.HW = HW; a.P = P; a.C = C; a.fgamma = focal_gamma; a.tau = tau; a.gamma_per = gamma_per; a.w6 = nullptr; a.dice = dice;
-  hipLaunchKernelGGL(loss_pixel_k<true>, dim3((unsigned)cdiv64(P, LP_BLOCK)), dim3(LP_BLOCK), 0, st, a);
+  if (C <= LP_MAXC) loss_pixel_dice_launch<LP_MAXC>(a, parts, dice, st);
+  else loss_pixel_dice_launch<LP_WIDE_MAXC>(a, parts, dice, st);
   PMF_LAUNCH_CHECK();
   return 0;
 }
+extern "C" int pmf_loss_pixel_dice(const float* lidar_prob, const float* camera_prob, const int64_t* label, const float* alpha,
+                                   int32_t N, int32_t C, int64_t HW, float focal_gamma, float tau, float gamma_per,
+                                   unsigned long long* cnt, float* grad_lidar, float* grad_camera, float* key, double* rows,
+                                   unsigned long long* conf_lidar, unsigned long long* conf_camera, double* parts,
+                                   double* dice, pmf_stream_t s) {
+  return loss_pixel_dice_impl(LP_MAXC, lidar_prob, camera_prob, label, alpha, N, C, HW, focal_gamma, tau, gamma_per, cnt,
+                              grad_lidar, grad_camera, key, rows, conf_lidar, conf_camera, parts, dice, s);
+}
 
-extern "C" int pmf_loss_dice_finish(const double* dice, int32_t C, float* out10, pmf_stream_t s) {
-  if (!dice || !out10 || C < 2 || C > LP_MAXC) return PMF_E_ARG;
+static int loss_dice_finish_impl(int maxc, const double* dice, int32_t C, float* out10, pmf_stream_t s) {
+  if (!dice || !out10 || C < 2 || C > maxc) return PMF_E_ARG;
   hipLaunchKernelGGL(loss_dice_finish_k, dim3(1), dim3(64), 0, (hipStream_t)s, dice, (int)C, out10);
   PMF_LAUNCH_CHECK();
   return 0;
+}
+extern "C" int pmf_loss_dice_finish(const double* dice, int32_t C, float* out10, pmf_stream_t s) {
+  return loss_dice_finish_impl(LP_MAXC, dice, C, out10, s);
 }
 
 static int loss_lovasz_impl(const int64_t* perm, const float* key_sorted, const int64_t* label, int32_t N, int32_t C,
@@ -890,11 +926,11 @@ extern "C" int64_t pmf_loss_sort_workspace(int32_t C, int64_t P) {
   return 4 * (int64_t)2 * C * P * 4 + (int64_t)2 * C * 256 * nb * 4;       // 2 key + 2 value buffers, histograms
 }
 
-static int loss_lovasz_sort_impl(const float* key, const int64_t* label, int32_t N, int32_t C, int64_t HW,
+static int loss_lovasz_sort_impl(int maxc, const float* key, const int64_t* label, int32_t N, int32_t C, int64_t HW,
                                  const unsigned long long* cnt, float lambda, float gamma_per, const float* w6, void* ws,
                                  float* bsum, double* dots, const double* rows, float* grad_lidar, float* grad_camera,
                                  float* out8, pmf_stream_t s) {
-  if (C < 2 || C > LP_MAXC || N < 1 || HW < 1 || !ws) return PMF_E_ARG;
+  if (C < 2 || C > maxc || N < 1 || HW < 1 || !ws) return PMF_E_ARG;
   if (HW > LV_MAXP || (int64_t)N * HW > LV_MAXP) return PMF_E_UNSUPPORTED;
   const int64_t P = (int64_t)N * HW;
   const int nb = (int)cdiv64(P, RS_CHUNK), R = 2 * C;
@@ -939,13 +975,41 @@ extern "C" int pmf_loss_lovasz_sort(const float* key, const int64_t* label, int3
                                     const unsigned long long* cnt, float lambda, float gamma_per, void* workspace, float* bsum,
                                     double* dots, const double* rows, float* grad_lidar, float* grad_camera, float* out8,
                                     pmf_stream_t s) {
-  return loss_lovasz_sort_impl(key, label, N, C, HW, cnt, lambda, gamma_per, nullptr, workspace, bsum, dots, rows, grad_lidar,
+  return loss_lovasz_sort_impl(LP_MAXC, key, label, N, C, HW, cnt, lambda, gamma_per, nullptr, workspace, bsum, dots, rows, grad_lidar,
                                grad_camera, out8, s);
 }
 extern "C" int pmf_loss_lovasz_sort_w(const float* key, const int64_t* label, int32_t N, int32_t C, int64_t HW,
                                       const unsigned long long* cnt, const float* w6, void* workspace, float* bsum, double* dots,
                                       const double* rows, float* grad_lidar, float* grad_camera, float* out8, pmf_stream_t s) {
   if (!w6) return PMF_E_ARG;
-  return loss_lovasz_sort_impl(key, label, N, C, HW, cnt, 0.f, 0.f, w6, workspace, bsum, dots, rows, grad_lidar, grad_camera,
+  return loss_lovasz_sort_impl(LP_MAXC, key, label, N, C, HW, cnt, 0.f, 0.f, w6, workspace, bsum, dots, rows, grad_lidar, grad_camera,
                                out8, s);
+}
+
+// ---- 33..64 classes (include/pmf_amd_wide.h) -------------------------------------------------------------------------
+// The guards are the narrow entry points' with the class limit at LP_WIDE_MAXC; C <= LP_MAXC launches the very <LP_MAXC>
+// kernels.  The Lovasz stage (radix sort, Jaccard kernels, fold) has no capacity of its own: only its guard moves.
+extern "C" int pmf_loss_pixel_wide(const float* lidar_prob, const float* camera_prob, const int64_t* label, const float* alpha,
+                                   int32_t N, int32_t C, int64_t HW, float focal_gamma, float tau, float gamma_per,
+                                   unsigned long long* cnt, float* grad_lidar, float* grad_camera, float* key, double* rows,
+                                   unsigned long long* conf_lidar, unsigned long long* conf_camera, double* parts,
+                                   double* dice, const float* w6, pmf_stream_t s) {
+  if ((parts == nullptr) != (dice == nullptr) || (w6 && dice)) return PMF_E_ARG;
+  if (dice)
+    return loss_pixel_dice_impl(LP_WIDE_MAXC, lidar_prob, camera_prob, label, alpha, N, C, HW, focal_gamma, tau, gamma_per,
+                                cnt, grad_lidar, grad_camera, key, rows, conf_lidar, conf_camera, parts, dice, s);
+  return loss_pixel_impl(LP_WIDE_MAXC, lidar_prob, camera_prob, label, alpha, N, C, HW, focal_gamma, tau,
+                         w6 ? 0.f : gamma_per, w6, cnt, grad_lidar, grad_camera, key, rows, conf_lidar, conf_camera, s);
+}
+
+extern "C" int pmf_loss_lovasz_sort_wide(const float* key, const int64_t* label, int32_t N, int32_t C, int64_t HW,
+                                         const unsigned long long* cnt, float lambda, float gamma_per, void* workspace,
+                                         float* bsum, double* dots, const double* rows, float* grad_lidar, float* grad_camera,
+                                         float* out8, const float* w6, pmf_stream_t s) {
+  return loss_lovasz_sort_impl(LP_WIDE_MAXC, key, label, N, C, HW, cnt, w6 ? 0.f : lambda, w6 ? 0.f : gamma_per, w6,
+                               workspace, bsum, dots, rows, grad_lidar, grad_camera, out8, s);
+}
+
+extern "C" int pmf_loss_dice_finish_wide(const double* dice, int32_t C, float* out10, pmf_stream_t s) {
+  return loss_dice_finish_impl(LP_WIDE_MAXC, dice, C, out10, s);
 }

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include "../../include/pmf_amd.h"
+#include "../../include/pmf_amd_wide.h"
 
 extern "C" int pmf_pack_weights_batched(const pmf_pack_job_t*, int32_t, int32_t, pmf_stream_t);
 
@@ -128,9 +129,12 @@ static int run_one_(const pmf_op_t& o, pmf_stream_t s) {
       if (a.p[2]) return pmf_colsum_rows((const float*)a.p[0], i[0], a.l[0], i[1], (float*)a.p[1], i[2], (float*)a.p[2], s);
       return pmf_colsum((const float*)a.p[0], i[0], a.l[0], i[1], (float*)a.p[1], i[2], s);
     case PMF_OP_SOFTMAX:  // p: logits prob | i: ldc N HW C ident (1: the logits go out as they are)
+      if (i[3] > 32) return pmf_softmax_wide((const float*)a.p[0], i[0], i[1], i[2], i[3], i[4], (float*)a.p[1], s);
       if (i[4]) return pmf_logits_nhwc_to_nchw((const float*)a.p[0], i[0], i[1], i[2], i[3], (float*)a.p[1], s);
       return pmf_softmax_nhwc_to_nchw((const float*)a.p[0], i[0], i[1], i[2], i[3], (float*)a.p[1], s);
     case PMF_OP_SOFTMAX_BWD:  // p: prob g dlogits | i: N HW C ldc ident
+      if (i[2] > 32)
+        return pmf_softmax_wide_bwd((const float*)a.p[0], (const float*)a.p[1], i[0], i[1], i[2], i[4], (float*)a.p[2], i[3], s);
       if (i[4]) return pmf_logits_bwd_nchw_to_nhwc((const float*)a.p[1], i[0], i[1], i[2], (float*)a.p[2], i[3], s);
       return pmf_softmax_bwd_nchw_to_nhwc((const float*)a.p[0], (const float*)a.p[1], i[0], i[1], i[2], (float*)a.p[2],
                                           i[3], s);

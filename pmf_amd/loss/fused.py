@@ -18,6 +18,34 @@ _SORT_WS = {}
 MAX_PIXELS = 1 << 24       # the Lovasz stage counts ranks in float32 (include/pmf_amd.h): more pixels are PMF_E_UNSUPPORTED
 
 
+def _wide(c):
+    """True: the class count needs the entry points of include/pmf_amd_wide.h (33..64 classes); up to 32 the calls are the
+    ones of pmf_amd.h, unchanged.  More classes than the library takes is an error here, not a code from the library."""
+    if c > L.WIDE_CLASSES:
+        raise ValueError("pmf_amd fused loss: %d classes, the fused objective takes at most %d" % (c, L.WIDE_CLASSES))
+    return c > L.NARROW_CLASSES
+
+
+def _pixel_wide(lib, pl, pc, lab, a, n, c, hw, focal_gamma, tau, gamma_per, cnt, gl, gc, key, rows, conf_l, conf_c, parts,
+                dice, w6, st):
+    L.check(lib.pmf_loss_pixel_wide(pl.data_ptr(), pc.data_ptr(), lab.data_ptr(), a.data_ptr(), n, c, hw, float(focal_gamma),
+                                    float(tau), float(gamma_per), cnt.data_ptr(), gl.data_ptr(), gc.data_ptr(),
+                                    key.data_ptr(), rows.data_ptr(), conf_l.data_ptr() if conf_l is not None else None,
+                                    conf_c.data_ptr() if conf_c is not None else None,
+                                    parts.data_ptr() if parts is not None else None,
+                                    dice.data_ptr() if dice is not None else None,
+                                    w6.data_ptr() if w6 is not None else None, st), "pmf_loss_pixel_wide")
+
+
+def _lovasz_sort_wide(lib, key, lab, n, c, hw, p, cnt, lambda_, gamma_per, bsum, dots, rows, gl, gc, out, w6, st):
+    ws = _sort_workspace(lib, c, p, key.device)
+    _check_lovasz(lib.pmf_loss_lovasz_sort_wide(key.data_ptr(), lab.data_ptr(), n, c, hw, cnt.data_ptr(), float(lambda_),
+                                                float(gamma_per), ws.data_ptr(), bsum.data_ptr(), dots.data_ptr(),
+                                                rows.data_ptr(), gl.data_ptr(), gc.data_ptr(), out.data_ptr(),
+                                                w6.data_ptr() if w6 is not None else None, st),
+                  "pmf_loss_lovasz_sort_wide", p)
+
+
 def _check_lovasz(rc, what, p):
     if rc != 0:
         L.check(rc, "%s on N*H*W = %d pixels (the Lovasz stage takes at most 2^24 = %d)" % (what, p, MAX_PIXELS))
@@ -59,6 +87,7 @@ class _FusedPMFLoss(torch.autograd.Function):
         pl, pc = lidar_prob.detach().contiguous().float(), camera_prob.detach().contiguous().float()
         lab = label.contiguous().long()
         n, c, h, w = pl.shape
+        wide = _wide(c)
         hw, p = h * w, n * h * w
         dev = pl.device
         gl, gc = _grad_buffers(pl, pc, grad_out)
@@ -71,22 +100,27 @@ class _FusedPMFLoss(torch.autograd.Function):
         out6 = torch.empty(8, dtype=torch.float32, device=dev)
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         a = alpha.to(dev, torch.float32).contiguous()
-        L.check(lib.pmf_loss_pixel(pl.data_ptr(), pc.data_ptr(), lab.data_ptr(), a.data_ptr(), n, c, hw,
-                                   float(focal_gamma), float(tau), float(gamma_per), cnt.data_ptr(), gl.data_ptr(),
-                                   gc.data_ptr(), key.data_ptr(), rows.data_ptr(),
-                                   conf_l.data_ptr() if conf_l is not None else None,
-                                   conf_c.data_ptr() if conf_c is not None else None, st), "pmf_loss_pixel")
-        if _use_torch_sort():
-            vals, perm = torch.sort(key, dim=1, descending=True)
-            _check_lovasz(lib.pmf_loss_lovasz(perm.data_ptr(), vals.data_ptr(), lab.data_ptr(), n, c, hw, cnt.data_ptr(),
-                                              float(lambda_), float(gamma_per), bsum.data_ptr(), dots.data_ptr(), rows.data_ptr(),
-                                              gl.data_ptr(), gc.data_ptr(), out6.data_ptr(), st), "pmf_loss_lovasz", p)
-        else:       # labelled pixels of the classes present only, sorted in the library (no torch.sort, no int64 indices)
-            ws = _sort_workspace(lib, c, p, dev)
-            _check_lovasz(lib.pmf_loss_lovasz_sort(key.data_ptr(), lab.data_ptr(), n, c, hw, cnt.data_ptr(), float(lambda_),
-                                                   float(gamma_per), ws.data_ptr(), bsum.data_ptr(), dots.data_ptr(),
-                                                   rows.data_ptr(), gl.data_ptr(), gc.data_ptr(), out6.data_ptr(), st),
-                          "pmf_loss_lovasz_sort", p)
+        if wide:
+            _pixel_wide(lib, pl, pc, lab, a, n, c, hw, focal_gamma, tau, gamma_per, cnt, gl, gc, key, rows, conf_l, conf_c,
+                        None, None, None, st)
+            _lovasz_sort_wide(lib, key, lab, n, c, hw, p, cnt, lambda_, gamma_per, bsum, dots, rows, gl, gc, out6, None, st)
+        else:
+            L.check(lib.pmf_loss_pixel(pl.data_ptr(), pc.data_ptr(), lab.data_ptr(), a.data_ptr(), n, c, hw,
+                                       float(focal_gamma), float(tau), float(gamma_per), cnt.data_ptr(), gl.data_ptr(),
+                                       gc.data_ptr(), key.data_ptr(), rows.data_ptr(),
+                                       conf_l.data_ptr() if conf_l is not None else None,
+                                       conf_c.data_ptr() if conf_c is not None else None, st), "pmf_loss_pixel")
+            if _use_torch_sort():
+                vals, perm = torch.sort(key, dim=1, descending=True)
+                _check_lovasz(lib.pmf_loss_lovasz(perm.data_ptr(), vals.data_ptr(), lab.data_ptr(), n, c, hw, cnt.data_ptr(),
+                                                  float(lambda_), float(gamma_per), bsum.data_ptr(), dots.data_ptr(), rows.data_ptr(),
+                                                  gl.data_ptr(), gc.data_ptr(), out6.data_ptr(), st), "pmf_loss_lovasz", p)
+            else:       # labelled pixels of the classes present only, sorted in the library (no torch.sort, no int64 indices)
+                ws = _sort_workspace(lib, c, p, dev)
+                _check_lovasz(lib.pmf_loss_lovasz_sort(key.data_ptr(), lab.data_ptr(), n, c, hw, cnt.data_ptr(), float(lambda_),
+                                                       float(gamma_per), ws.data_ptr(), bsum.data_ptr(), dots.data_ptr(),
+                                                       rows.data_ptr(), gl.data_ptr(), gc.data_ptr(), out6.data_ptr(), st),
+                              "pmf_loss_lovasz_sort", p)
         ctx.save_for_backward(gl, gc)
         ctx.mark_non_differentiable(out6)
         return out6[0].clone(), out6
@@ -112,6 +146,7 @@ class _FusedWeightedLoss(torch.autograd.Function):
         lab = label.contiguous().long()
         w = w6.detach().contiguous().float()
         n, c, h, wd = pl.shape
+        wide = _wide(c)
         hw, p = h * wd, n * h * wd
         dev = pl.device
         gl, gc = _grad_buffers(pl, pc, grad_out)
@@ -124,21 +159,26 @@ class _FusedWeightedLoss(torch.autograd.Function):
         out8 = torch.empty(8, dtype=torch.float32, device=dev)
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         a = alpha.to(dev, torch.float32).contiguous()
-        L.check(lib.pmf_loss_pixel_w(pl.data_ptr(), pc.data_ptr(), lab.data_ptr(), a.data_ptr(), n, c, hw,
-                                     float(focal_gamma), float(tau), w.data_ptr(), cnt.data_ptr(), gl.data_ptr(),
-                                     gc.data_ptr(), key.data_ptr(), rows.data_ptr(),
-                                     conf_l.data_ptr() if conf_l is not None else None,
-                                     conf_c.data_ptr() if conf_c is not None else None, st), "pmf_loss_pixel_w")
-        if _use_torch_sort():
-            vals, perm = torch.sort(key, dim=1, descending=True)
-            _check_lovasz(lib.pmf_loss_lovasz_w(perm.data_ptr(), vals.data_ptr(), lab.data_ptr(), n, c, hw, cnt.data_ptr(),
-                                                w.data_ptr(), bsum.data_ptr(), dots.data_ptr(), rows.data_ptr(), gl.data_ptr(),
-                                                gc.data_ptr(), out8.data_ptr(), st), "pmf_loss_lovasz_w", p)
+        if wide:
+            _pixel_wide(lib, pl, pc, lab, a, n, c, hw, focal_gamma, tau, 0.0, cnt, gl, gc, key, rows, conf_l, conf_c, None,
+                        None, w, st)
+            _lovasz_sort_wide(lib, key, lab, n, c, hw, p, cnt, 0.0, 0.0, bsum, dots, rows, gl, gc, out8, w, st)
         else:
-            ws = _sort_workspace(lib, c, p, dev)
-            _check_lovasz(lib.pmf_loss_lovasz_sort_w(key.data_ptr(), lab.data_ptr(), n, c, hw, cnt.data_ptr(), w.data_ptr(),
-                                                     ws.data_ptr(), bsum.data_ptr(), dots.data_ptr(), rows.data_ptr(),
-                                                     gl.data_ptr(), gc.data_ptr(), out8.data_ptr(), st), "pmf_loss_lovasz_sort_w", p)
+            L.check(lib.pmf_loss_pixel_w(pl.data_ptr(), pc.data_ptr(), lab.data_ptr(), a.data_ptr(), n, c, hw,
+                                         float(focal_gamma), float(tau), w.data_ptr(), cnt.data_ptr(), gl.data_ptr(),
+                                         gc.data_ptr(), key.data_ptr(), rows.data_ptr(),
+                                         conf_l.data_ptr() if conf_l is not None else None,
+                                         conf_c.data_ptr() if conf_c is not None else None, st), "pmf_loss_pixel_w")
+            if _use_torch_sort():
+                vals, perm = torch.sort(key, dim=1, descending=True)
+                _check_lovasz(lib.pmf_loss_lovasz_w(perm.data_ptr(), vals.data_ptr(), lab.data_ptr(), n, c, hw, cnt.data_ptr(),
+                                                    w.data_ptr(), bsum.data_ptr(), dots.data_ptr(), rows.data_ptr(), gl.data_ptr(),
+                                                    gc.data_ptr(), out8.data_ptr(), st), "pmf_loss_lovasz_w", p)
+            else:
+                ws = _sort_workspace(lib, c, p, dev)
+                _check_lovasz(lib.pmf_loss_lovasz_sort_w(key.data_ptr(), lab.data_ptr(), n, c, hw, cnt.data_ptr(), w.data_ptr(),
+                                                         ws.data_ptr(), bsum.data_ptr(), dots.data_ptr(), rows.data_ptr(),
+                                                         gl.data_ptr(), gc.data_ptr(), out8.data_ptr(), st), "pmf_loss_lovasz_sort_w", p)
         terms = torch.stack([out8[1], out8[2], out8[3], out8[4], out8[6], out8[7]])
         ctx.save_for_backward(gl, gc, terms)
         ctx.mark_non_differentiable(out8)
@@ -165,6 +205,7 @@ class _FusedSensatLoss(torch.autograd.Function):
         pl, pc = lidar_prob.detach().contiguous().float(), camera_prob.detach().contiguous().float()
         lab = label.contiguous().long()
         n, c, h, w = pl.shape
+        wide = _wide(c)
         hw, p = h * w, n * h * w
         dev = pl.device
         gl, gc = _grad_buffers(pl, pc, grad_out)
@@ -179,18 +220,24 @@ class _FusedSensatLoss(torch.autograd.Function):
         out10 = torch.empty(10, dtype=torch.float32, device=dev)
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         a = alpha.to(dev, torch.float32).contiguous()
-        L.check(lib.pmf_loss_pixel_dice(pl.data_ptr(), pc.data_ptr(), lab.data_ptr(), a.data_ptr(), n, c, hw,
-                                        float(focal_gamma), float(tau), float(gamma_per), cnt.data_ptr(), gl.data_ptr(),
-                                        gc.data_ptr(), key.data_ptr(), rows.data_ptr(),
-                                        conf_l.data_ptr() if conf_l is not None else None,
-                                        conf_c.data_ptr() if conf_c is not None else None, parts.data_ptr(),
-                                        dice.data_ptr(), st), "pmf_loss_pixel_dice")
-        ws = _sort_workspace(lib, c, p, dev)
-        _check_lovasz(lib.pmf_loss_lovasz_sort(key.data_ptr(), lab.data_ptr(), n, c, hw, cnt.data_ptr(), float(lambda_),
-                                               float(gamma_per), ws.data_ptr(), bsum.data_ptr(), dots.data_ptr(),
-                                               rows.data_ptr(), gl.data_ptr(), gc.data_ptr(), out10.data_ptr(), st),
-                      "pmf_loss_lovasz_sort", p)
-        L.check(lib.pmf_loss_dice_finish(dice.data_ptr(), c, out10.data_ptr(), st), "pmf_loss_dice_finish")
+        if wide:
+            _pixel_wide(lib, pl, pc, lab, a, n, c, hw, focal_gamma, tau, gamma_per, cnt, gl, gc, key, rows, conf_l, conf_c,
+                        parts, dice, None, st)
+            _lovasz_sort_wide(lib, key, lab, n, c, hw, p, cnt, lambda_, gamma_per, bsum, dots, rows, gl, gc, out10, None, st)
+            L.check(lib.pmf_loss_dice_finish_wide(dice.data_ptr(), c, out10.data_ptr(), st), "pmf_loss_dice_finish_wide")
+        else:
+            L.check(lib.pmf_loss_pixel_dice(pl.data_ptr(), pc.data_ptr(), lab.data_ptr(), a.data_ptr(), n, c, hw,
+                                            float(focal_gamma), float(tau), float(gamma_per), cnt.data_ptr(), gl.data_ptr(),
+                                            gc.data_ptr(), key.data_ptr(), rows.data_ptr(),
+                                            conf_l.data_ptr() if conf_l is not None else None,
+                                            conf_c.data_ptr() if conf_c is not None else None, parts.data_ptr(),
+                                            dice.data_ptr(), st), "pmf_loss_pixel_dice")
+            ws = _sort_workspace(lib, c, p, dev)
+            _check_lovasz(lib.pmf_loss_lovasz_sort(key.data_ptr(), lab.data_ptr(), n, c, hw, cnt.data_ptr(), float(lambda_),
+                                                   float(gamma_per), ws.data_ptr(), bsum.data_ptr(), dots.data_ptr(),
+                                                   rows.data_ptr(), gl.data_ptr(), gc.data_ptr(), out10.data_ptr(), st),
+                          "pmf_loss_lovasz_sort", p)
+            L.check(lib.pmf_loss_dice_finish(dice.data_ptr(), c, out10.data_ptr(), st), "pmf_loss_dice_finish")
         ctx.save_for_backward(gl, gc)
         ctx.mark_non_differentiable(out10)
         return out10[0].clone(), out10

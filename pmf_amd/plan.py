@@ -636,6 +636,9 @@ class Plan(PlanConvMixin, PlanTuneMixin, PlanRunMixin):
         themselves (SalsaNext(softmax=False), salsanext.py:167,206-207)."""
         t = logits
         ident = int(not softmax)
+        if t.C > L.WIDE_CLASSES:      # (33..64: plan.cpp takes the entry points of include/pmf_amd_wide.h)
+            raise ValueError("softmax_out(%s): %d classes, the softmax and the fused objective take at most %d"
+                             % (name or slot, t.C, L.WIDE_CLASSES))
 
         def f(op):
             s = op.u.sm
