@@ -4,7 +4,8 @@ The header is the only place a constant, a struct member or a signature is writt
 PMF_* integers, the ctypes structs and the argtypes / restype of every prototype.  The reader is strict -- a declaration it
 cannot classify raises PMFLibraryError naming it, it never skips or guesses.  include/pmf_amd_sensat.h (the SensatUrban
 training loader) is a second header read the same way on top of the first: EXPORTS_SENSAT, BevSample.  include/pmf_amd_wide.h
-(33 to 64 classes in the heads and the fused objective) is a third: EXPORTS_WIDE.
+(33 to 64 classes in the heads and the fused objective) is a third: EXPORTS_WIDE.  include/pmf_amd_a2d2.h (the A2D2 loader:
+undistortion map, remap, per-point pass) is a fourth: EXPORTS_A2D2, LENS_TELECAM / LENS_FISHEYE.
 
 The product path has NO fallback: if the header or the shared library is missing, or the library's struct layout
 disagrees with the header, importing a compute entry point raises.
@@ -19,6 +20,7 @@ LIB_PATH = os.path.join(_HERE, "libpmf_amd.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "pmf_amd.h")
 SENSAT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "pmf_amd_sensat.h")
 WIDE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "pmf_amd_wide.h")
+A2D2_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "pmf_amd_a2d2.h")
 
 
 class PMFLibraryError(RuntimeError):
@@ -211,6 +213,8 @@ _H = _read()
 _HS = _read(SENSAT_HEADER_PATH, _SENSAT_STRUCT_NAMES, _H)
 # 33..64 classes (csrc/elementwise.hip, csrc/loss.hip): prototypes only, no struct and no constant
 _HW = _read(WIDE_HEADER_PATH, {}, _H)
+# the A2D2 loader (csrc/undistort.hip, csrc/a2d2.hip): prototypes and the two lens kinds
+_HA = _read(A2D2_HEADER_PATH, {}, _H)
 # PMF_ACT_RELU -> ACT_RELU, PMF_OP_CONV -> OP_CONV, PMF_MAX_SRC -> MAX_SRC ...; the error codes keep their prefix (PMF_E_ARG)
 globals().update((k if k.startswith("PMF_E_") else k[4:], v) for k, v in _H.consts.items() if k.startswith("PMF_"))
 globals().update((py, _H.structs[c]) for c, py in _STRUCT_NAMES.items())
@@ -221,13 +225,16 @@ globals().update((k[4:], v) for k, v in _HS.consts.items() if k.startswith("PMF_
 globals().update((py, _HS.structs[c]) for c, py in _SENSAT_STRUCT_NAMES.items())
 EXPORTS_SENSAT = list(_HS.protos)       # every function pmf_amd_sensat.h declares
 EXPORTS_WIDE = list(_HW.protos)         # every function pmf_amd_wide.h declares
+EXPORTS_A2D2 = list(_HA.protos)         # every function pmf_amd_a2d2.h declares
+globals().update((k[4:], v) for k, v in _HA.consts.items() if k.startswith("PMF_"))      # LENS_TELECAM, LENS_FISHEYE
 NARROW_CLASSES, WIDE_CLASSES = 32, 64   # class limit of pmf_amd.h's softmax / loss entry points, and of pmf_amd_wide.h's
 
 
 def bind(handle):
     """Set restype and argtypes of every function of the header that `handle` (a CDLL of this library, or of a private
     build of some of its sources) exports; returns the handle."""
-    for name, (restype, argtypes) in list(_H.protos.items()) + list(_HS.protos.items()) + list(_HW.protos.items()):
+    for name, (restype, argtypes) in list(_H.protos.items()) + list(_HS.protos.items()) + list(_HW.protos.items()) \
+            + list(_HA.protos.items()):
         fn = getattr(handle, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes
@@ -256,6 +263,9 @@ def lib():
     missing = [name for name in EXPORTS_WIDE if not hasattr(L, name)]
     if missing:
         raise PMFLibraryError("pmf_amd: %s lacks %s, which include/pmf_amd_wide.h declares" % (LIB_PATH, ", ".join(missing)))
+    missing = [name for name in EXPORTS_A2D2 if not hasattr(L, name)]
+    if missing:
+        raise PMFLibraryError("pmf_amd: %s lacks %s, which include/pmf_amd_a2d2.h declares" % (LIB_PATH, ", ".join(missing)))
     if L.pmf_wide_max_classes() != WIDE_CLASSES:
         raise PMFLibraryError("pmf_amd: %s takes up to %d classes, the binding expects %d"
                               % (LIB_PATH, L.pmf_wide_max_classes(), WIDE_CLASSES))

@@ -6,4 +6,5 @@ from .preprocess import augmentor, projection  # noqa: F401
 from . import semantic_kitti  # noqa: F401
 from . import nuScenes  # noqa: F401
 from . import sensat_urban  # noqa: F401
+from . import a2d2  # noqa: F401
 from .sensat_urban import SensatUrban, SensatLoader, compute_bev_feature  # noqa: F401

@@ -15,7 +15,11 @@ A ``NuscenesV2``-type dataset -- one with ``mapLidar2CameraCropYaw(seq_id, point
 (row, col) f64[K,2], keep bool[P])`` and no ``proj_matrix`` -- keeps its geometry on the host (the devkit's chain of rigid
 transforms, dataset_nuscenes_v2.py:301-375); what the loader does with the result (:72-141: truncation, bounding box, depth
 of the camera-frame points, last-writer-wins scatter, labelMapping as a 256-entry table, RGB window) is one packed upload +
-pmf_project_v2_scatter.  Validation only: the training path on such a dataset is not implemented."""
+pmf_project_v2_scatter.  Validation only: the training path on such a dataset is not implemented.
+A dataset with ``projectDevice(index, image_dev, img_scale) -> (proj, xy_index, depth, keep, extra)`` and
+``loadImageDevice(index)`` (A2D2_PV: pixel coordinates come with the frame, every point is kept) is served in all three
+layouts -- training, validation, return_uproj -- and by _eval_item: image on the device, ColorJitter, the same rescale draw
+and host resize as above, the dataset's own projection, then the common pad / crop tail (:42-157).  That check comes first."""
 import ctypes as C
 import math
 
@@ -94,6 +98,40 @@ class PerspectiveViewLoaderV2(Dataset):
             self.aug_ops = FlipRotateCrop(self.pv_config["proj_ht"], self.pv_config["proj_wt"])
         self._nus_lut = self._ident = None            # NuscenesV2-type datasets: label table, identity source indices
 
+    def _has_project_device(self):
+        return hasattr(self.dataset, "projectDevice")
+
+    def _device_frame(self, index, train):
+        """a dataset with projectDevice: -> (proj, xy_index, depth, keep, extra); the draws and their order are those of the
+        SemanticKITTI path (jitter, then the rescale when ``train``)"""
+        dev = torch.device(self.device)
+        if dev.type != "cuda":
+            raise RuntimeError("PerspectiveViewLoaderV2 runs on the GPU only (device=%s)" % self.device)
+        image = self.dataset.loadImageDevice(index)
+        if self.img_jitter is not None:
+            image = self.img_jitter(image)
+        img_scale = 1.0
+        if train:
+            from PIL import Image               # :50-57, as below: numpy's global RNG, PIL's bilinear resize on the host
+            image = Image.fromarray(image.cpu().numpy())
+            img_w, img_h = image.size
+            img_scale = np.random.uniform(low=1.0, high=1.2)
+            image = np.asarray(image.resize((int(img_w * img_scale), int(img_h * img_scale)), Image.BILINEAR))
+        return self.dataset.projectDevice(index, image, img_scale)
+
+    def _tail(self, proj):
+        """:142-157 bottom / centred horizontal zero padding, then flip / rotate / crop (training) or the centre crop"""
+        ch, cw = (self.pv_config["proj_ht"], self.pv_config["proj_wt"]) if self.is_train else \
+            (self.pv_config["proj_h"], self.pv_config["proj_w"])
+        _, h, w = proj.shape
+        mh, mw = max(ch, h), max(cw, w)
+        left = (mw - w) // 2
+        padded = torch.nn.functional.pad(proj, (left, mw - w - left, 0, mh - h))
+        if self.is_train:
+            return self.aug_ops(padded)
+        top, lft = int(round((mh - ch) / 2.0)), int(round((mw - cw) / 2.0))
+        return padded[:, top:top + ch, lft:lft + cw].contiguous()
+
     def _is_nus_v2(self):
         return hasattr(self.dataset, "mapLidar2CameraCropYaw") and not hasattr(self.dataset, "proj_matrix")
 
@@ -156,6 +194,11 @@ class PerspectiveViewLoaderV2(Dataset):
         return out, xy, dep, keep.bool(), extra, pointcloud
 
     def __getitem__(self, index):
+        if self._has_project_device():
+            proj, xy, depth, keep, _ = self._device_frame(index, self.is_train)
+            if self.return_uproj:
+                return proj, xy, depth, keep, torch.as_tensor(np.asarray(self.dataset.loadPointcloud(index)))
+            return self._tail(proj)
         if self._is_nus_v2():
             proj, xy, depth, keep, _, pointcloud = self._nus_item(index)
             if not self.return_uproj:
@@ -193,21 +236,14 @@ class PerspectiveViewLoaderV2(Dataset):
                                                      self.dataset.class_map_lut, fl, fr, self.device, img_scale)
         if self.return_uproj:
             return proj, xy, depth, keep, torch.as_tensor(np.asarray(pointcloud))
-        ch, cw = (self.pv_config["proj_ht"], self.pv_config["proj_wt"]) if self.is_train else \
-            (self.pv_config["proj_h"], self.pv_config["proj_w"])
-        _, h, w = proj.shape
-        mh, mw = max(ch, h), max(cw, w)
-        left = (mw - w) // 2
-        padded = torch.nn.functional.pad(proj, (left, mw - w - left, 0, mh - h))      # :142-147
-        if self.is_train:
-            return self.aug_ops(padded)
-        top, lft = int(round((mh - ch) / 2.0)), int(round((mw - cw) / 2.0))            # CenterCrop (:36-39)
-        return padded[:, top:top + ch, lft:lft + cw].contiguous()
+        return self._tail(proj)
 
     def _eval_item(self, index):
         """validation frame for the evaluation task (return_uproj layout): (proj, xy_index, depth, keep, extra) with
         ``extra`` the device tensors of _project_frame_v2; the public return tuple of __getitem__ is unchanged.  On a
         NuscenesV2-type dataset ``src`` is the position of each kept point in the sweep and ``sem`` the sweep's raw labels."""
+        if self._has_project_device():
+            return self._device_frame(index, False)
         if self._is_nus_v2():
             return self._nus_item(index)[:5]
         image = self.dataset.loadImage(index)

@@ -93,6 +93,18 @@ class Trainer(base.Trainer):
             self.cls_weight[0] = 0
             self.ignore_class = [0]
             self.mapped_cls_name = trainset.mapped_cls_name
+        elif s.dataset == "a2d2":                                              # trainer.py:169-189
+            here = os.path.dirname(os.path.abspath(__file__))
+            kw = dict(camsLidars_path=os.path.join(here, s.config["cams_lidars_path"]),
+                      classIndex_path=os.path.join(here, s.config["class_index_path"]))
+            # optional: unused_index / zero_size_index / split_bounds of A2D2_PV, for a tree smaller than the full data set
+            kw.update(s.config.get("a2d2_subset") or {})
+            trainset = pc_processor.dataset.a2d2.A2D2_PV(root=s.data_root, split="train", **kw)
+            valset = pc_processor.dataset.a2d2.A2D2_PV(root=s.data_root, split="valid", **kw)
+            self.cls_weight = 1 / (cls_freq + 1e-8)
+            self.cls_weight[0] = 0
+            self.ignore_class = [0]
+            self.mapped_cls_name = trainset.mapped_class_name
         elif s.dataset == "Synthetic":
             nfr = s.config.get("synthetic_frames", [16, 4])
             train_pv = SyntheticPV2(nfr[0], pv["proj_ht"], pv["proj_wt"], s.nclasses, seed=s.seed)
