@@ -149,7 +149,20 @@ int pmf_conv_fwd(const pmf_conv_desc_t* d, pmf_stream_t s);
  * Two stages: per-block partial sums into `partial` (workspace, >= pmf_conv_wgrad_workspace() bytes),
  * then a deterministic reduction that writes the gradient in the PyTorch OIHW layout
  *   dw_oihw[(co*Cin_real + k)*KHW + tap_widx[t]]   (k < Cin_real; padded channels are dropped).
- * Replaces the weight half of aten::convolution_backward for every conv of the path. */
+ * Replaces the weight half of aten::convolution_backward for every conv of the path.
+ * Padding lanes: the dz columns [Cout, dz_ldc), the operands' pitch padding [C, ldc) and the channels [Cin_real, Ktot) may hold
+ * anything, NaN included: a kernel may load them, but only into slab rows / columns that stage 2 never reads.  `partial` need
+ * not be initialised.  nsplit: what pmf_conv_wgrad_nsplit returns; the kernels are written for any other count >= 1 with a
+ * workspace sized for it (the streaming family: a multiple of N, else PMF_E_ARG), a split that gets no pixel writing a slab of
+ * zeros -- tested at 1 (N), the default and one count with empty splits per family, not beyond.  tap_widx may name a subset of the window: the other
+ * entries of dw_oihw are left alone.
+ * PMF_E_ARG without a launch, from all three entry points: a null dz, partial, dw_oihw or operand x; N, OH, OW, Cout, KHW or
+ * Cin_real < 1; Cin_real > Ktot; dz_ldc < Cout; a tap_widx[t] outside [0, KHW); dbias_rows without dbias_out or with
+ * dbias_ld < Cout; in_stride other than 1 or 2; an operand C that is no multiple of 8 or ldc no multiple of 4; nsplit < 1;
+ * reserved0 != 0.  The stage-1 launch path (pmf_conv_wgrad, pmf_conv_wgrad_partial) also refuses, without a launch: a dz that
+ * is not 8-byte aligned in the direct one-tap families and a streaming split count that is no multiple of N (PMF_E_ARG);
+ * a kernel that would need more than 160 KiB of LDS, or a shape its family has no instantiation for (PMF_E_UNSUPPORTED).
+ * (tests/test_wgrad_reference_host.py, tests/test_gpu_wgrad.py) */
 typedef struct {
   int32_t N, OH, OW, Cout;
   int32_t nsrc;

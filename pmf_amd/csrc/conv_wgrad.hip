@@ -2349,6 +2349,19 @@ static int wgrad_phases(const pmf_wgrad_desc_t* d, pmf_stream_t st, int phase) {
   for (int i = 0; i < d->nsrc; ++i)
     if (d->src[i].C % 8 || d->src[i].ldc % 4) return PMF_E_ARG;
   if (d->reserved0) return PMF_E_ARG;
+  // the same descriptor serves both stages (the plan fills it once), so both stages check all of it
+  if (!d->dz || !d->partial || !d->dw_oihw || d->dz_ldc < d->Cout) return PMF_E_ARG;
+  if (d->N < 1 || d->OH < 1 || d->OW < 1 || d->Cout < 1 || d->KHW < 1 || d->Cin_real < 1) return PMF_E_ARG;
+  if (d->in_stride != 1 && d->in_stride != 2) return PMF_E_ARG;
+  int Ktot = 0;
+  for (int i = 0; i < d->nsrc; ++i) {
+    if (!d->src[i].x || d->src[i].C < 8) return PMF_E_ARG;
+    Ktot += d->src[i].C;
+  }
+  if (d->Cin_real > Ktot) return PMF_E_ARG;
+  for (int t = 0; t < d->ntaps; ++t)       // (stage 2 writes dw_oihw[... * KHW + tap_widx[t]])
+    if (d->tap_widx[t] < 0 || d->tap_widx[t] >= d->KHW) return PMF_E_ARG;
+  if (d->dbias_rows && (!d->dbias_out || d->dbias_nrows < 0 || d->dbias_ld < d->Cout)) return PMF_E_ARG;
   WgPick p;
   wg_pick(d, &p);
   if (phase & 1) {
