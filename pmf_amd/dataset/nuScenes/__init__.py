@@ -1,10 +1,20 @@
-"""``pc_processor.dataset.nuScenes`` (pc_processor/dataset/nuScenes/dataset_nuscenes.py:74-282): the reader sits on the
-third-party nuscenes-devkit (NuScenes tables, LidarPointCloud, view_points), which is not part of this image.  The name
-resolves so that tasks/pmf/trainer.py:127-136 reaches a clear message instead of an AttributeError; everything behind the
-dataset -- the per-camera-view loader (nus_perspective_loader.py), the six-camera inference loop
-(tasks/pmf_eval_nuscenes/infer.py), the merge with the LiDAR-only fallback (postproc/merge.py) -- is built and tested on a
-devkit-free stand-in with the same attributes (oracle/cases.py SyntheticNus, tests only)."""
+"""``pc_processor.dataset.nuScenes``.  The reference's readers (pc_processor/dataset/nuScenes/dataset_nuscenes.py:74-282,
+dataset_nuscenes_v2.py:77-375) sit on the third-party nuscenes-devkit; here ``tables.py`` reads the JSON tables itself and
+runs the per-point chain of transforms on the device (``open_nuscenes`` -> ``NuscenesNative`` / ``NuscenesV2Native``), which
+is what the task entry points build.  ``Nuscenes`` / ``NuscenesV2`` keep their names and only raise, as before.  Everything
+behind the dataset -- the per-camera-view loader (nus_perspective_loader.py), the six-camera inference loop
+(tasks/pmf_eval_nuscenes/infer.py), the merge with the LiDAR-only fallback (postproc/merge.py) -- takes any object with the
+readers' attributes (tests: oracle/cases.py SyntheticNus)."""
 from .nus_perspective_loader import NusPerspectiveViewLoader  # noqa: F401
+from . import tables  # noqa: F401
+from .tables import NuTables, NuscenesNative, NuscenesV2Native, quaternion_rotation_matrix  # noqa: F401
+
+
+def open_nuscenes(v2, root, version="v1.0-trainval", split="train", **kw):
+    """The devkit-free readers of tables.py under one name: ``NuscenesV2Native`` (the EPMF reader) when ``v2``, else
+    ``NuscenesNative``.  ``kw``: has_image, splits_path (JSON scene lists, needed for v1.0-trainval when nuscenes-devkit
+    is absent), device.  What the task entry points call; ``Nuscenes`` / ``NuscenesV2`` below keep their behaviour."""
+    return (NuscenesV2Native if v2 else NuscenesNative)(root, version=version, split=split, **kw)
 
 
 class Nuscenes(object):

@@ -17,7 +17,8 @@ transforms, dataset_nuscenes_v2.py:301-375); what the loader does with the resul
 of the camera-frame points, last-writer-wins scatter, labelMapping as a 256-entry table, RGB window) is one packed upload +
 pmf_project_v2_scatter.  Validation only: the training path on such a dataset is not implemented.
 A dataset with ``projectDevice(index, image_dev, img_scale) -> (proj, xy_index, depth, keep, extra)`` and
-``loadImageDevice(index)`` (A2D2_PV: pixel coordinates come with the frame, every point is kept) is served in all three
+``loadImageDevice(index)`` (A2D2_PV: pixel coordinates come with the frame, every point is kept; NuscenesV2Native:
+pmf_nus_project in front of the scatter) is served in all three
 layouts -- training, validation, return_uproj -- and by _eval_item: image on the device, ColorJitter, the same rescale draw
 and host resize as above, the dataset's own projection, then the common pad / crop tail (:42-157).  That check comes first."""
 import ctypes as C

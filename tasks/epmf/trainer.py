@@ -86,9 +86,11 @@ class Trainer(base.Trainer):
                 if self.cls_weight[cl] < 1e-10:
                     self.ignore_class.append(cl)
             self.mapped_cls_name = trainset.mapped_cls_name
-        elif s.dataset == "nuScenes":                                          # trainer.py:152-167 (needs nuscenes-devkit)
-            trainset = pc_processor.dataset.nuScenes.Nuscenes(root=s.data_root, version="v1.0-trainval", split="train")
-            valset = pc_processor.dataset.nuScenes.Nuscenes(root=s.data_root, version="v1.0-trainval", split="val")
+        elif s.dataset == "nuScenes":                                          # trainer.py:152-167
+            version = "v1.0-mini" if s.is_debug else "v1.0-trainval"
+            kw = dict(splits_path=s.config.get("nus_splits"))
+            trainset = pc_processor.dataset.nuScenes.open_nuscenes(True, s.data_root, version, "train", **kw)
+            valset = pc_processor.dataset.nuScenes.open_nuscenes(True, s.data_root, version, "val", **kw)
             self.cls_weight = 1 / (cls_freq + 1e-8)
             self.cls_weight[0] = 0
             self.ignore_class = [0]

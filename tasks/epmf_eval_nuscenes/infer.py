@@ -9,7 +9,7 @@ into the sweep's running (confidence, label) pair where strictly more confident 
 view (pmf_eval_sweep_finish): the points some camera labelled non-zero are scored, and with save_pred_results the uint8
 labels go to <save_path>/preds/lidarseg/<val|test>/<lidar_token>_lidarseg.bin.  After the loop the reference's report:
 point-wise and pixel-wise mean / per-class IoU, Acc and Recall, the LaTeX row, class distribution, fwIoU, and the
-confusion / Acc / Recall matrices.  The dataset object is the devkit's business (pc_processor.dataset.nuScenes.NuscenesV2);
+confusion / Acc / Recall matrices.  The dataset is read without nuscenes-devkit (pc_processor.dataset.nuScenes.open_nuscenes);
 any object with its attributes can be passed in: Experiment(settings, dataset=...).
 
 With the optional key sub_pred_folder (a folder written by tasks/salsanext_eval_nuscenes: preds/lidarseg/<val|test>/
@@ -100,7 +100,8 @@ class Inference(object):
                 version, split = "v1.0-trainval", "val"
             else:
                 version, split = "v1.0-test", "test"
-            dataset = pc_processor.dataset.nuScenes.NuscenesV2(root=s.data_root, version=version, split=split)
+            dataset = pc_processor.dataset.nuScenes.open_nuscenes(True, s.data_root, version, split,
+                                                                  splits_path=s.config.get("nus_splits"))
         # batch 1, views in order (the reference's DataLoader(batch_size=1, shuffle=False)); the scatter runs on the device
         return pc_processor.dataset.PerspectiveViewLoaderV2(dataset=dataset, config=s.config, is_train=False,
                                                             return_uproj=True)

@@ -207,13 +207,11 @@ class Trainer(object):
                 self.recorder.logger.info("focal_loss alpha: {}".format(self.alpha))
             self.mapped_cls_name = trainset.mapped_cls_name
         elif s.dataset == "nuScenes":                                          # trainer.py:127-136
-            trainset = pc_processor.dataset.nuScenes.Nuscenes(root=s.data_root, version="v1.0-trainval", split="train")
-            valset = pc_processor.dataset.nuScenes.Nuscenes(root=s.data_root, version="v1.0-trainval", split="val")
-            self.cls_weight = np.ones((s.nclasses))
-            self.alpha = np.ones(s.nclasses, np.float32)
-            self.alpha[0] = 0
-            self.ignore_class = [0]
-            self.mapped_cls_name = trainset.mapped_cls_name
+            # PerspectiveViewLoader projects with the dataset's proj_matrix; the nuScenes readers have a chain of transforms
+            # per view instead (pc_processor.dataset.nuScenes.open_nuscenes, served by the EPMF loader)
+            raise NotImplementedError("PMF training on nuScenes is not implemented: PerspectiveViewLoader needs "
+                                      "dataset.proj_matrix, which a nuScenes reader does not have.  tasks/epmf trains on "
+                                      "nuScenes (config_server_nus.yaml); tasks/pmf_eval_nuscenes evaluates a PMF model on it")
         elif s.dataset == "Synthetic":
             nfr = s.config.get("synthetic_frames", [16, 4])
             train_pv = SyntheticPV(nfr[0], sensor["proj_ht"], sensor["proj_wt"], s.nclasses, seed=s.seed)

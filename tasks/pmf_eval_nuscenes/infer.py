@@ -7,8 +7,8 @@ camera sees, read at their pixel or voted by the KNN post-processing -> kept tog
 confidences.  After the sixth view (:171-200): getMergePred (per point the label of the most confident camera, HIP:
 pmf_merge_pred) -- with a LiDAR-only SalsaNext standing in for the points no camera sees when ``fallback`` is configured
 (more_experiment_config.md:10) -- then -1 -> 0, int32, ``<save_path>/preds/lidarseg/<split>/<lidar_token>_lidarseg.bin`` and
-the point-wise / pixel-wise confusion matrices.  The dataset object is the devkit's business
-(pc_processor.dataset.nuScenes.Nuscenes); any object with its attributes can be passed in (tests: oracle.cases.SyntheticNus).
+the point-wise / pixel-wise confusion matrices.  The dataset is read without nuscenes-devkit
+(pc_processor.dataset.nuScenes.open_nuscenes); any object with its attributes can be passed in (tests: oracle.cases.SyntheticNus).
 
     python infer.py config_server_nus.yaml
 """
@@ -78,7 +78,8 @@ class Inference(object):
                 version, split = "v1.0-trainval", "val"
             else:
                 version, split = "v1.0-test", "test"
-            dataset = pc_processor.dataset.nuScenes.Nuscenes(root=s.data_root, version=version, split=split)
+            dataset = pc_processor.dataset.nuScenes.open_nuscenes(False, s.data_root, version, split,
+                                                                  splits_path=s.config.get("nus_splits"))
         loader = NusPerspectiveViewLoader(dataset=dataset, config=s.config)
         return loader, loader            # frames are visited in order, one at a time, on the device (:98-104: batch 1)
 

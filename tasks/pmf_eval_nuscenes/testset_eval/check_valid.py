@@ -99,11 +99,11 @@ class Experiment(object):
                 LidarSegEval(nusc, eval_set=self.eval_set, verbose=True, results_folder=self.results_folder).evaluate()
             return
         dataset = self.dataset
-        if dataset is None:                       # (raises ImportError: the table reader needs the devkit)
+        if dataset is None:
             import pc_processor
-            dataset = pc_processor.dataset.nuScenes.Nuscenes(
-                root=s.data_root, version="v1.0-trainval" if s.has_label else "v1.0-test", split=self.eval_set,
-                has_image=False)
+            dataset = pc_processor.dataset.nuScenes.open_nuscenes(
+                False, s.data_root, "v1.0-trainval" if s.has_label else "v1.0-test", self.eval_set, has_image=False,
+                splits_path=s.config.get("nus_splits"))
         faults = check_submission(self.results_folder, self.eval_set, dataset_point_counts(dataset), s.n_classes)
         for f in faults:
             print(f)

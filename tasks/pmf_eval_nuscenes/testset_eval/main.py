@@ -9,7 +9,7 @@ are read on the host, one packed upload, one pmf_eval_fill launch (fused uint8 l
 device-to-host copy.  Output, as the reference writes it: <save_path>/<experiment_id>/preds/lidarseg/<val|test>/
 <lidar_token>_lidarseg.bin (uint8) and preds/<val|test>/submission.json; then the reference's report (point-wise table, LaTeX
 row, class distribution, fwIoU, confusion / Acc / Recall matrices) as plain-text tables, plus the share of points by source.
-The dataset object is the devkit's business (pc_processor.dataset.nuScenes.Nuscenes(has_image=False)); any object with
+The dataset is read without nuscenes-devkit (pc_processor.dataset.nuScenes.open_nuscenes, has_image=False); any object with
 token_list, loadLabelByIndex, labelMapping (or map_name_from_general_index_to_segmentation_index) and mapped_cls_name can be
 passed in: Experiment(settings, dataset=...).  check_valid.py validates the written folder.
 
@@ -144,8 +144,8 @@ class MergePred(object):
                 version, split = "v1.0-trainval", "val"
             else:
                 version, split = "v1.0-test", "test"
-            dataset = pc_processor.dataset.nuScenes.Nuscenes(root=s.data_root, version=version, split=split,
-                                                             has_image=False)
+            dataset = pc_processor.dataset.nuScenes.open_nuscenes(False, s.data_root, version, split, has_image=False,
+                                                                  splits_path=s.config.get("nus_splits"))
         return dataset
 
     def _batch(self, idx, lut):

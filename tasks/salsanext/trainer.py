@@ -74,11 +74,10 @@ class Trainer(object):
 
     def _initDataloader(self):
         s = self.settings
-        if s.dataset == "nuScenes":                                            # trainer.py:61-72 (needs nuscenes-devkit)
-            trainset = pc_processor.dataset.nuScenes.Nuscenes(root=s.data_root, version="v1.0-trainval", split="train",
-                                                              return_ref=False, has_image=False)
-            valset = pc_processor.dataset.nuScenes.Nuscenes(root=s.data_root, version="v1.0-trainval", split="val",
-                                                            return_ref=False, has_image=False)
+        if s.dataset == "nuScenes":                                            # trainer.py:61-72
+            kw = dict(return_ref=False, has_image=False, splits_path=s.config.get("nus_splits"))
+            trainset = pc_processor.dataset.nuScenes.open_nuscenes(False, s.data_root, "v1.0-trainval", "train", **kw)
+            valset = pc_processor.dataset.nuScenes.open_nuscenes(False, s.data_root, "v1.0-trainval", "val", **kw)
             self.mapped_cls_name = trainset.mapped_cls_name
             self.ignore_class = [0]
             self.cls_weight = np.ones((s.n_classes))

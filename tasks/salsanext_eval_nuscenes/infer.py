@@ -8,8 +8,8 @@ int32 labels + point confusion.  One device-to-host copy per batch; every sweep'
 <save_path>/preds/lidarseg/<val|test>/<lidar_token>_lidarseg.bin as int32 (what the reference's SalsaNext script writes).
 The last batch may be short: it runs at its own size (the model keeps one plan per input shape), nothing is padded.
 After the loop the reference's report: point-wise and pixel-wise mean / per-class IoU, Acc and Recall, the LaTeX row, class
-distribution, fwIoU, and the confusion / Acc / Recall matrices, as plain-text tables.  The dataset object is the devkit's
-business (pc_processor.dataset.nuScenes.Nuscenes(has_image=False)); any object with loadDataByIndex, labelMapping,
+distribution, fwIoU, and the confusion / Acc / Recall matrices, as plain-text tables.  The dataset is read without
+nuscenes-devkit (pc_processor.dataset.nuScenes.open_nuscenes, has_image=False); any object with loadDataByIndex, labelMapping,
 map_name_from_general_index_to_segmentation_index (or class_map_lut), mapped_cls_name and token_list can be passed in:
 Experiment(settings, dataset=...).
 
@@ -99,8 +99,8 @@ class Inference(object):
             if s.dataset not in ("NuScenes", "nuScenes"):
                 raise ValueError("invalid dataset: {}".format(s.dataset))
             version, split = ("v1.0-trainval", "val") if s.has_label else ("v1.0-test", "test")
-            dataset = pc_processor.dataset.nuScenes.Nuscenes(root=s.data_root, version=version, split=split,
-                                                             has_image=False)
+            dataset = pc_processor.dataset.nuScenes.open_nuscenes(False, s.data_root, version, split, has_image=False,
+                                                                  splits_path=s.config.get("nus_splits"))
         return pc_processor.dataset.SalsaNextLoader(dataset=dataset, config=s.config, data_len=s.data_len,
                                                     is_train=False, return_uproj=True)
 
