@@ -143,6 +143,25 @@ int pmf_conv_ws_ok(const pmf_conv_desc_t* d);
  * multiples of 16 channels, same H x W, no broadcast, Ktot * 32 * 6 bytes + tables within 160 KiB); 0 otherwise */
 int pmf_conv_s3_eligible(const pmf_conv_desc_t* d);
 
+/* What a launch reads, needs to be zero, and never writes (held by tests/test_conv_reference_host.py and
+ * tests/test_gpu_conv.py, which run every kernel family on guarded buffers):
+ *   reads      operand i up to N * H * W * ldc floats and no further -- a K rounded up beyond the pitch (24 channels of dz taken as
+ *              src.C = 32) reads the next pixel's first channels against zero weight rows and 0 past the tensor's end; scale,
+ *              shift [C]; cmul [N][cmul_ld]; the weight pack up to the edge of the last output-channel tile inside ldw; bias
+ *              [Cout]; ep_cmul [N][ep_cmul_ld]; ep_relu_x at the pixels it writes; ep_relu_scale / shift, ep_stat_mean [C];
+ *              splitk_ws: K splits x [N][OH][OW][Cout rounded up to 4] floats, every element written before it is read.  A
+ *              workspace too small for the requested split count is no error: the launch splits fewer times.
+ *   zero       the padded channels [C_real, C) of an operand AFTER its view (pitch padding [C, ldc) may hold anything, NaN
+ *              included); the pack's rows and columns beyond the layer's channels; the ticket array.
+ *   not written  the output's pitch padding [Cout, out_ldc) (per destination [C, out_ldc)); with out_sy / out_sx > 1 the
+ *              pixels of the other parity classes and those beyond OH x OW of this class; statistics rows beyond
+ *              pmf_conv_fwd_stat_rows(); any operand.  The ticket array reads all zero again after the launch.
+ * PMF_E_ARG without a launch: nsrc, ntaps, in_stride, a channel count or pitch off its grid (see the fields); N, OH, OW or
+ * Cout < 1; a null operand x, a null out (or dst[k].out); neither w nor w_s3; ndst > 0 where pmf_conv_multi_ok() is 0;
+ * ep_stat_mean without stats or without ep_relu_x; PMF_EP_STAT_X_ONLY without ep_stat_mean.  PMF_E_UNSUPPORTED without a launch: w_s3
+ * on a descriptor no split-bf16 kernel takes (per-tap staging, an operand that is broadcast or no multiple of 16 channels, a
+ * stride-2 window other than all nine taps of a 3x3, ldw no multiple of 32); a tensor of 2 GiB or more; more than 160 KiB of
+ * LDS. */
 int pmf_conv_fwd(const pmf_conv_desc_t* d, pmf_stream_t s);
 
 /* Weight gradient (+ nothing else): dW[t][k][co] = sum_{n,oy,ox} in_t(n, oy*s+tdy, ox*s+tdx, k) * dz[n,oy,ox,co].

@@ -1239,7 +1239,7 @@ __global__ __launch_bounds__(256) void conv_finish_k(const pmf_conv_desc_t d, in
             if (d.ep_relu_scale) xr = xr * d.ep_relu_scale[c + k] + d.ep_relu_shift[c + k];
             if (!(xr > 0.f) && !(d.ep_flags & PMF_EP_STAT_X_ONLY)) x = 0.f;
           }
-          if (d.accumulate) x += op[k];
+          x += d.accumulate ? op[k] : 0.f;     // (+ 0: a -0 leaves as +0, as from the epilogue of conv_epi.h)
           if (vec) xo[k] = x; else op[k] = x;
           s1[k] += (double)x;
           s2[k] += (double)x * (double)(d.ep_stat_mean ? xraw - d.ep_stat_mean[c + k] : x);
@@ -1674,9 +1674,21 @@ static int conv_args(const pmf_conv_desc_t* d) {
   return 0;
 }
 
+// what only a launch needs: a shape with something to compute, an operand and a destination to address
+static int conv_launch_args(const pmf_conv_desc_t* d) {
+  if (d->N < 1 || d->OH < 1 || d->OW < 1 || d->Cout < 1) return PMF_E_ARG;
+  for (int i = 0; i < d->nsrc; ++i)
+    if (!d->src[i].x) return PMF_E_ARG;
+  if (d->ndst <= 0 && !d->out) return PMF_E_ARG;
+  for (int k = 0; k < d->ndst && k < PMF_MAX_SRC; ++k)
+    if (!d->dst[k].out) return PMF_E_ARG;
+  return 0;
+}
+
 extern "C" int pmf_conv_fwd(const pmf_conv_desc_t* d, pmf_stream_t st) {
   hipStream_t s = (hipStream_t)st;
   if (const int rc = conv_args(d)) return rc;
+  if (const int rc = conv_launch_args(d)) return rc;
   ConvPick p;
   conv_pick(d, &p);
   if (p.rc) return p.rc;

@@ -21,12 +21,16 @@ def from_nhwc(t, c):
     return t[..., :c].permute(0, 3, 1, 2).contiguous().cpu()
 
 
-def pack_fwd(w, k_pad, ldw):
-    """OIHW -> [taps][k_pad][ldw] (host-side reference packing for single-op tests)."""
+def pack_fwd_host(w, k_pad, ldw):
+    """OIHW -> [taps][k_pad][ldw] float32 on the host (reference packing for single-op tests)."""
     co, ci, kh, kw = w.shape
     p = torch.zeros(kh * kw, k_pad, ldw)
     p[:, :ci, :co] = w.permute(2, 3, 1, 0).reshape(kh * kw, ci, co)
-    return p.cuda().contiguous()
+    return p.contiguous()
+
+
+def pack_fwd(w, k_pad, ldw):
+    return pack_fwd_host(w, k_pad, ldw).cuda()
 
 
 def split_bf16(x):
@@ -39,7 +43,7 @@ def split_bf16(x):
     return h1, h2, h3
 
 
-def pack_fwd_s3(w, k_pad, ldw):
+def pack_fwd_s3_host(w, k_pad, ldw):
     """OIHW -> split-bf16 MFMA B fragments [taps][k_pad/16][ldw/32][3][64 lanes][8] (pmf_conv_desc_t.w_s3): element
     (tap, k, n) sits in fragment (tap, k/16, n/32) at lane n%32 + 32*((k%16)/8), slot k%8."""
     co, ci, kh, kw = w.shape
@@ -48,10 +52,14 @@ def pack_fwd_s3(w, k_pad, ldw):
     planes = torch.stack([h.view(torch.int16) for h in split_bf16(p)], 0)          # [3][t][k][n]
     f = planes.view(3, kh * kw, k_pad // 16, 2, 8, ldw // 32, 32)                   # p t ks kh ke ct nl
     f = f.permute(1, 2, 5, 0, 3, 6, 4).contiguous()                                # t ks ct p kh nl ke
-    return f.cuda()
+    return f
 
 
-def pack_fwd_s3_stem(w, ldw):
+def pack_fwd_s3(w, k_pad, ldw):
+    return pack_fwd_s3_host(w, k_pad, ldw).cuda()
+
+
+def pack_fwd_s3_stem_host(w, ldw):
     """stem class (one operand of 8 padded channels, many taps): pmf_pack_job_t format 2 -- ONE virtual tap whose K index is
     tap * 8 + channel, K padded to a multiple of 16"""
     co, ci, kh, kw = w.shape
@@ -62,7 +70,45 @@ def pack_fwd_s3_stem(w, ldw):
     p[0, :kh * kw * 8, :co] = q.reshape(kh * kw * 8, co)
     planes = torch.stack([h.view(torch.int16) for h in split_bf16(p)], 0)
     f = planes.view(3, 1, kp // 16, 2, 8, ldw // 32, 32).permute(1, 2, 5, 0, 3, 6, 4).contiguous()
-    return f.cuda()
+    return f
+
+
+def pack_fwd_s3_stem(w, ldw):
+    return pack_fwd_s3_stem_host(w, ldw).cuda()
+
+
+SENT = 0x7FC0BEEF                     # a quiet NaN with a payload (as a pair of words: a float64 NaN as well)
+BAND = 1024                           # floats: 4 KiB on either side
+
+
+class GBuf:
+    """n float32 on the device between two guard bands; body: an array of 4-byte elements (copied bit for bit) or None = the
+    NaN sentinel everywhere"""
+
+    def __init__(self, n, body=None, dev="cuda"):
+        self.n = int(n)
+        raw = np.full(BAND + self.n + BAND, SENT, np.uint32).view(np.int32)
+        if body is not None:
+            b = np.ascontiguousarray(body)
+            if b.dtype.itemsize != 4:
+                b = b.astype(np.float32)
+            b = b.reshape(-1)
+            assert b.size == self.n
+            raw[BAND:BAND + self.n] = b.view(np.int32)
+        self.before = raw
+        self.raw = torch.from_numpy(raw.copy()).to(dev)
+        self.ptr = self.raw.data_ptr() + 4 * BAND
+        assert self.ptr % 16 == 0
+
+    def bands_ok(self, what):
+        lo, hi = self.raw[:BAND].cpu().numpy(), self.raw[BAND + self.n:].cpu().numpy()
+        assert (lo.view(np.uint32) == SENT).all() and (hi.view(np.uint32) == SENT).all(), "%s: a guard band was written" % what
+
+    def unchanged(self, what):
+        assert np.array_equal(self.raw.cpu().numpy(), self.before), "%s: an input was written" % what
+
+    def body(self):
+        return self.raw[BAND:BAND + self.n].cpu().numpy().view(np.float32)
 
 
 def stream():

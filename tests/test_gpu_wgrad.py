@@ -36,42 +36,13 @@ pytestmark = pytest.mark.gpu
 
 from pmf_amd import _lib as L  # noqa: E402
 from tests import wgrad_cases as W  # noqa: E402
-from tests.gpu_helpers import stream  # noqa: E402
+from tests.gpu_helpers import BAND, SENT, GBuf, stream  # noqa: E402,F401
 
-DEV = "cuda"
-SENT = 0x7FC0BEEF                     # a quiet NaN with a payload
-BAND = 1024                           # floats: 4 KiB on either side
 U32 = 2.0 ** -24
 NAMES = [c.name for c in W.CASES]
 TILE_NAMES = [n for n in NAMES if W.BY_NAME[n].fam[(1, "swp_pixel_split")] != W.BY_NAME[n].fam[(1, "default")]
               or W.instantiation(W.BY_NAME[n], 1, "nsplit_two_tiles") != W.instantiation(W.BY_NAME[n], 1, "default")]
 S3_FAMILIES = ("SWP", "NSPLIT", "DIRECT_S3")
-
-
-class GBuf:
-    """n float32 between two guard bands; body: a float32 array (copied bit for bit) or None = the NaN sentinel everywhere"""
-
-    def __init__(self, n, body=None):
-        self.n = int(n)
-        raw = np.full(BAND + self.n + BAND, SENT, np.uint32).view(np.int32)
-        if body is not None:
-            b = np.ascontiguousarray(body, np.float32).reshape(-1)
-            assert b.size == self.n
-            raw[BAND:BAND + self.n] = b.view(np.int32)
-        self.before = raw
-        self.raw = torch.from_numpy(raw.copy()).to(DEV)
-        self.ptr = self.raw.data_ptr() + 4 * BAND
-        assert self.ptr % 16 == 0
-
-    def bands_ok(self, what):
-        lo, hi = self.raw[:BAND].cpu().numpy(), self.raw[BAND + self.n:].cpu().numpy()
-        assert (lo.view(np.uint32) == SENT).all() and (hi.view(np.uint32) == SENT).all(), "%s: a guard band was written" % what
-
-    def unchanged(self, what):
-        assert np.array_equal(self.raw.cpu().numpy(), self.before), "%s: an input was written" % what
-
-    def body(self):
-        return self.raw[BAND:BAND + self.n].cpu().numpy().view(np.float32)
 
 
 def bits(a):
@@ -394,8 +365,8 @@ def test_reduce_multi_is_bitwise_the_single_reductions(monkeypatch):
         meta[8 * j:8 * j + 8] = list(row)
     assert kinds == {0, 1}
     raw = np.frombuffer(bytes(descs), np.uint8)
-    jobs_dev = torch.from_numpy(raw.copy()).to(DEV)
-    meta_dev = torch.from_numpy(np.array(list(meta), np.int32)).to(DEV)
+    jobs_dev = torch.from_numpy(raw.copy()).to("cuda")
+    meta_dev = torch.from_numpy(np.array(list(meta), np.int32)).to("cuda")
     assert jobs_dev.data_ptr() % 8 == 0
     rc = lib.pmf_conv_wgrad_reduce_multi(jobs_dev.data_ptr(), meta_dev.data_ptr(), len(jobs), total, stream())
     assert rc == 0
