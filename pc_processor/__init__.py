@@ -8,6 +8,7 @@ for _n in ("salsanext_loader", "perspective_view_loader", "perspective_view_load
            "nuScenes", "sensat_urban", "a2d2"):
     _sys.modules["pc_processor.dataset." + _n] = getattr(dataset, _n)
 _sys.modules["pc_processor.dataset.semantic_kitti.parser"] = dataset.semantic_kitti.parser
+_sys.modules["pc_processor.dataset.semantic_kitti.fov"] = dataset.semantic_kitti.fov
 _sys.modules["pc_processor.dataset.preprocess.augmentor"] = dataset.preprocess.augmentor
 _sys.modules["pc_processor.dataset.preprocess.projection"] = dataset.preprocess.projection
 _sys.modules["pc_processor.dataset.sensat_urban.sensat_urban"] = dataset.sensat_urban.sensat_urban

@@ -5,6 +5,7 @@
 // Order-preserving compaction (x_data / y_data) = block counts -> single-block scan -> ballot prefix.
 // The winner per pixel is an atomicMax over point indices, then one gather pass builds the [10,h,w] tensor.
 #include "common.h"
+#include "../../include/pmf_amd_fov.h"
 
 // bit-exact float32 / float64 arithmetic: no fused contraction except the explicit fma() calls below
 #pragma clang fp contract(off)
@@ -262,6 +263,100 @@ extern "C" int pmf_project_scatter2(const float* points, const int32_t* sem, int
   const int g = (int)cdiv64(hw, 256);
   hipLaunchKernelGGL(proj_gather_tag_k, dim3(g > 2048 ? 2048 : g), dim3(256), 0, st, points, sem, depth, image, lut, nlut,
                      (const unsigned*)pix_tag, (unsigned)generation, h, w, proj_out, (unsigned long long*)slots, n_kept);
+  PMF_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- SemanticKITTI-FOV filter (include/pmf_amd_fov.h; tasks/process_semantickitti_fov/create_fov_dataset.py) -----------
+// The reference keeps, per frame, the rows whose projection falls inside the image, and writes them and their label words.
+// Here a BATCH of frames goes through one pass: count (keep mask by project_point under the dims of the frame that owns
+// the row, kept rows per workgroup) -> the single-block scan above -> compact (rows and label words copied as bits to
+// their place in file order).  A workgroup may straddle frames: every lane finds its frame in the offsets table (LDS).
+static_assert(PB == PMF_FOV_BLOCK, "pmf_amd_fov.h sizes blk_cnt by the workgroup of these kernels");
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+// offsets[0 .. B] -> LDS
+__device__ __forceinline__ void fov_stage(const int64_t* __restrict__ offsets, int B, int64_t* s_off) {
+  if ((int)threadIdx.x <= B) s_off[threadIdx.x] = offsets[threadIdx.x];
+  __syncthreads();
+}
+
+// the largest b in [0, B - 1] with s_off[b] <= i: the frame that owns row i (empty frames own nothing)
+__device__ __forceinline__ int fov_frame(const int64_t* s_off, int B, int64_t i) {
+  int lo = 0, hi = B - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (s_off[mid] <= i) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+__global__ __launch_bounds__(PB) void fov_count_k(const float* __restrict__ pts, const int64_t* __restrict__ offsets,
+                                                  const int32_t* __restrict__ dims, int B, int64_t P,
+                                                  const double* __restrict__ m, uint8_t* __restrict__ keep,
+                                                  int32_t* __restrict__ blk_cnt) {
+  __shared__ int64_t s_off[PMF_FOV_MAX_FRAMES + 1];
+  __shared__ int s_dim[2 * PMF_FOV_MAX_FRAMES];
+  if ((int)threadIdx.x < 2 * B) s_dim[threadIdx.x] = dims[threadIdx.x];
+  fov_stage(offsets, B, s_off);
+  const int64_t i = blockIdx.x * (int64_t)PB + threadIdx.x;
+  int k = 0;
+  if (i < P) {
+    const int b = fov_frame(s_off, B, i);
+    const f32x4 q = *(const f32x4*)(pts + i * 4);
+    const float pt[4] = {q.x, q.y, q.z, q.w};
+    int r, c;
+    k = project_point(pt, m, s_dim[2 * b], s_dim[2 * b + 1], r, c) ? 1 : 0;
+    keep[i] = (uint8_t)k;
+  }
+  const int cnt = __syncthreads_count(k);
+  if (threadIdx.x == 0) blk_cnt[blockIdx.x] = cnt;
+}
+
+// blk_off: the scanned counts, blk_off[gridDim.x] = the total.  The lane of the first row of frame b knows how many rows are
+// kept in front of it: that is out_offsets[b]; the lane of the last row of the batch writes the entries that equal P.
+__global__ __launch_bounds__(PB) void fov_compact_k(const u32x4* __restrict__ rows, const uint32_t* __restrict__ labels,
+                                                    const int64_t* __restrict__ offsets, int B, int64_t P,
+                                                    const uint8_t* __restrict__ keep, const int32_t* __restrict__ blk_off,
+                                                    u32x4* __restrict__ out_rows, uint32_t* __restrict__ out_labels,
+                                                    int64_t* __restrict__ out_offsets) {
+  __shared__ int64_t s_off[PMF_FOV_MAX_FRAMES + 1];
+  __shared__ int wave_cnt[PB / 64];
+  fov_stage(offsets, B, s_off);
+  const int64_t i = blockIdx.x * (int64_t)PB + threadIdx.x;
+  const bool k = i < P && keep[i] != 0;
+  const unsigned long long bal = __ballot(k);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int before = __popcll(bal & ((1ull << lane) - 1ull));
+  if (lane == 0) wave_cnt[wv] = __popcll(bal);
+  __syncthreads();
+  if (i >= P) return;
+  int woff = 0;
+  for (int j = 0; j < wv; ++j) woff += wave_cnt[j];
+  const int64_t dst = (int64_t)blk_off[blockIdx.x] + woff + before;      // kept rows in front of row i
+  for (int j = fov_frame(s_off, B, i); j >= 0 && s_off[j] == i; --j) out_offsets[j] = dst;
+  if (i == P - 1)
+    for (int j = B; j >= 1 && s_off[j] >= P; --j) out_offsets[j] = dst + (k ? 1 : 0);
+  if (k) {
+    out_rows[dst] = rows[i];                 // one 16-byte load, one 16-byte store
+    if (labels) out_labels[dst] = labels[i];
+  }
+}
+
+extern "C" int pmf_fov_filter(const float* points, const uint32_t* labels, const int64_t* offsets, const int32_t* dims,
+                              int32_t B, int64_t P_total, const double* proj, uint8_t* keep, float* out_points,
+                              uint32_t* out_labels, int64_t* out_offsets, int32_t* blk_cnt, pmf_stream_t s) {
+  hipStream_t st = (hipStream_t)s;
+  if (!points || !offsets || !dims || !proj || !keep || !out_points || !out_offsets || !blk_cnt) return PMF_E_ARG;
+  if (labels && !out_labels) return PMF_E_ARG;
+  if (B < 1 || B > PMF_FOV_MAX_FRAMES || P_total < 1) return PMF_E_ARG;
+  if ((((uintptr_t)points) | ((uintptr_t)out_points)) & 15) return PMF_E_ARG;
+  if (P_total >= ((int64_t)1 << 31)) return PMF_E_UNSUPPORTED;
+  const int nblk = (int)cdiv64(P_total, PB);
+  hipLaunchKernelGGL(fov_count_k, dim3(nblk), dim3(PB), 0, st, points, offsets, dims, B, P_total, proj, keep, blk_cnt);
+  hipLaunchKernelGGL(proj_scan_k, dim3(1), dim3(1024), 0, st, blk_cnt, nblk, blk_cnt + nblk);
+  hipLaunchKernelGGL(fov_compact_k, dim3(nblk), dim3(PB), 0, st, (const u32x4*)points, labels, offsets, B, P_total, keep,
+                     blk_cnt, (u32x4*)out_points, out_labels, out_offsets);
   PMF_LAUNCH_CHECK();
   return 0;
 }
