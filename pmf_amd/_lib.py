@@ -7,7 +7,8 @@ training loader) is a second header read the same way on top of the first: EXPOR
 (33 to 64 classes in the heads and the fused objective) is a third: EXPORTS_WIDE.  include/pmf_amd_a2d2.h (the A2D2 loader:
 undistortion map, remap, per-point pass) is a fourth: EXPORTS_A2D2, LENS_TELECAM / LENS_FISHEYE.  include/pmf_amd_nus.h (the
 nuScenes projection chain) is a fifth: EXPORTS_NUS, NUS_BLOCK, NUS_CHAIN, NUS_IMAGE / NUS_YAW.  include/pmf_amd_fov.h (the
-SemanticKITTI-FOV filter) is a sixth: EXPORTS_FOV, FOV_BLOCK, FOV_MAX_FRAMES.
+SemanticKITTI-FOV filter) is a sixth: EXPORTS_FOV, FOV_BLOCK, FOV_MAX_FRAMES.  include/pmf_amd_full.h (full sweeps from FOV
+predictions) is a seventh: EXPORTS_FULL, FULL_WS_PER_BLOCK, FULL_WS_FIXED.
 
 The product path has NO fallback: if the header or the shared library is missing, or the library's struct layout
 disagrees with the header, importing a compute entry point raises.
@@ -25,6 +26,7 @@ WIDE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "pmf_amd_wide
 A2D2_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "pmf_amd_a2d2.h")
 NUS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "pmf_amd_nus.h")
 FOV_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "pmf_amd_fov.h")
+FULL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "pmf_amd_full.h")
 
 
 class PMFLibraryError(RuntimeError):
@@ -223,6 +225,8 @@ _HA = _read(A2D2_HEADER_PATH, {}, _H)
 _HN = _read(NUS_HEADER_PATH, {}, _H)
 # the SemanticKITTI-FOV filter (csrc/project.hip): one prototype, the block size and the frames per call
 _HF = _read(FOV_HEADER_PATH, {}, _H)
+# full sweeps from FOV predictions (csrc/project.hip): one prototype and the two workspace constants
+_HK = _read(FULL_HEADER_PATH, {}, _H)
 # PMF_ACT_RELU -> ACT_RELU, PMF_OP_CONV -> OP_CONV, PMF_MAX_SRC -> MAX_SRC ...; the error codes keep their prefix (PMF_E_ARG)
 globals().update((k if k.startswith("PMF_E_") else k[4:], v) for k, v in _H.consts.items() if k.startswith("PMF_"))
 globals().update((py, _H.structs[c]) for c, py in _STRUCT_NAMES.items())
@@ -239,6 +243,8 @@ EXPORTS_NUS = list(_HN.protos)           # every function pmf_amd_nus.h declares
 globals().update((k[4:], v) for k, v in _HN.consts.items() if k.startswith("PMF_"))      # NUS_BLOCK, NUS_CHAIN, NUS_IMAGE, NUS_YAW
 EXPORTS_FOV = list(_HF.protos)           # every function pmf_amd_fov.h declares
 globals().update((k[4:], v) for k, v in _HF.consts.items() if k.startswith("PMF_"))      # FOV_BLOCK, FOV_MAX_FRAMES
+EXPORTS_FULL = list(_HK.protos)          # every function pmf_amd_full.h declares
+globals().update((k[4:], v) for k, v in _HK.consts.items() if k.startswith("PMF_"))      # FULL_WS_PER_BLOCK, FULL_WS_FIXED
 NARROW_CLASSES, WIDE_CLASSES = 32, 64   # class limit of pmf_amd.h's softmax / loss entry points, and of pmf_amd_wide.h's
 
 
@@ -246,7 +252,8 @@ def bind(handle):
     """Set restype and argtypes of every function of the header that `handle` (a CDLL of this library, or of a private
     build of some of its sources) exports; returns the handle."""
     for name, (restype, argtypes) in list(_H.protos.items()) + list(_HS.protos.items()) + list(_HW.protos.items()) \
-            + list(_HA.protos.items()) + list(_HN.protos.items()) + list(_HF.protos.items()):
+            + list(_HA.protos.items()) + list(_HN.protos.items()) + list(_HF.protos.items()) \
+            + list(_HK.protos.items()):
         fn = getattr(handle, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes
@@ -284,6 +291,9 @@ def lib():
     missing = [name for name in EXPORTS_FOV if not hasattr(L, name)]
     if missing:
         raise PMFLibraryError("pmf_amd: %s lacks %s, which include/pmf_amd_fov.h declares" % (LIB_PATH, ", ".join(missing)))
+    missing = [name for name in EXPORTS_FULL if not hasattr(L, name)]
+    if missing:
+        raise PMFLibraryError("pmf_amd: %s lacks %s, which include/pmf_amd_full.h declares" % (LIB_PATH, ", ".join(missing)))
     if L.pmf_wide_max_classes() != WIDE_CLASSES:
         raise PMFLibraryError("pmf_amd: %s takes up to %d classes, the binding expects %d"
                               % (LIB_PATH, L.pmf_wide_max_classes(), WIDE_CLASSES))

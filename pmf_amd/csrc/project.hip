@@ -6,6 +6,7 @@
 // The winner per pixel is an atomicMax over point indices, then one gather pass builds the [10,h,w] tensor.
 #include "common.h"
 #include "../../include/pmf_amd_fov.h"
+#include "../../include/pmf_amd_full.h"
 
 // bit-exact float32 / float64 arithmetic: no fused contraction except the explicit fma() calls below
 #pragma clang fp contract(off)
@@ -357,6 +358,174 @@ extern "C" int pmf_fov_filter(const float* points, const uint32_t* labels, const
   hipLaunchKernelGGL(proj_scan_k, dim3(1), dim3(1024), 0, st, blk_cnt, nblk, blk_cnt + nblk);
   hipLaunchKernelGGL(fov_compact_k, dim3(nblk), dim3(PB), 0, st, (const u32x4*)points, labels, offsets, B, P_total, keep,
                      blk_cnt, (u32x4*)out_points, out_labels, out_offsets);
+  PMF_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- full sweeps from FOV predictions (include/pmf_amd_full.h; tasks/pmf_eval_semantickitti/fullsweep_eval) --------------
+// The inverse of the filter above: count (project_point under the owning frame's dims; per workgroup the kept rows, the keep
+// bits of its 16 waves, and for every frame that starts inside it the kept rows in front of that start) -> the single-block
+// scan -> fill (the rank of a kept row inside its frame indexes the main words; one word out per row, confusion and source
+// counts through LDS).  Workspace: ws[0 .. nblk] counts / scanned counts and the total, ws[nblk + 1 ..] one entry per frame
+// start, then 32 words of keep bits per workgroup.
+#define FULL_MAXC 64
+#define FULL_GRID 512       // workgroups of the fill kernel: two of them fit a compute unit (18 KB of LDS, 16 waves each)
+static_assert(PMF_FULL_WS_PER_BLOCK == 1 + 2 * (PB / 64) && PMF_FULL_WS_FIXED == PMF_FOV_MAX_FRAMES + 2,
+              "pmf_amd_full.h sizes blk_cnt by the layout of these kernels");
+
+__global__ __launch_bounds__(PB) void full_count_k(const float* __restrict__ pts, const int64_t* __restrict__ offsets,
+                                                   const int32_t* __restrict__ dims, int B, int64_t P,
+                                                   const double* __restrict__ m, uint8_t* __restrict__ keep,
+                                                   int32_t* __restrict__ ws, int nblk) {
+  __shared__ int64_t s_off[PMF_FOV_MAX_FRAMES + 1];
+  __shared__ int s_dim[2 * PMF_FOV_MAX_FRAMES];
+  __shared__ int wave_cnt[PB / 64];
+  if ((int)threadIdx.x < 2 * B) s_dim[threadIdx.x] = dims[threadIdx.x];
+  fov_stage(offsets, B, s_off);
+  int32_t* start_in = ws + nblk + 1;
+  int32_t* bits = start_in + PMF_FOV_MAX_FRAMES + 1;
+  const int64_t i = blockIdx.x * (int64_t)PB + threadIdx.x;
+  int b = 0;
+  bool k = false;
+  if (i < P) {
+    b = fov_frame(s_off, B, i);
+    const f32x4 q = *(const f32x4*)(pts + i * 4);
+    const float pt[4] = {q.x, q.y, q.z, q.w};
+    int r, c;
+    k = project_point(pt, m, s_dim[2 * b], s_dim[2 * b + 1], r, c);
+    if (keep) keep[i] = k ? 1 : 0;
+  }
+  const unsigned long long bal = __ballot(k);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if (lane == 0) {
+    wave_cnt[wv] = __popcll(bal);
+    int32_t* w = bits + ((int64_t)blockIdx.x * (PB / 64) + wv) * 2;
+    w[0] = (int32_t)(uint32_t)bal;
+    w[1] = (int32_t)(uint32_t)(bal >> 32);
+  }
+  __syncthreads();
+  int before = __popcll(bal & ((1ull << lane) - 1ull));
+  for (int j = 0; j < wv; ++j) before += wave_cnt[j];
+  if (threadIdx.x == PB - 1) ws[blockIdx.x] = before + (k ? 1 : 0);
+  if (i < P)
+    for (int j = b; j >= 0 && s_off[j] == i; --j) start_in[j] = before;       // kept rows of this workgroup in front of frame j
+}
+
+__global__ __launch_bounds__(PB) void full_fill_k(const int64_t* __restrict__ offsets, int B, int64_t P,
+                                                  const int32_t* __restrict__ ws, int nblk,
+                                                  const uint32_t* __restrict__ main_ids,
+                                                  const int64_t* __restrict__ main_offsets, int64_t K_total,
+                                                  const uint32_t* __restrict__ sub_ids, const uint32_t* __restrict__ gt,
+                                                  const int32_t* __restrict__ lut, int nlut, uint32_t fill_id, int C,
+                                                  uint32_t* __restrict__ out, int64_t* __restrict__ kept_count,
+                                                  unsigned long long* __restrict__ counts,
+                                                  unsigned long long* __restrict__ conf) {
+  __shared__ int64_t s_off[PMF_FOV_MAX_FRAMES + 1];
+  __shared__ int64_t s_moff[PMF_FOV_MAX_FRAMES + 1];
+  __shared__ int64_t s_g[PMF_FOV_MAX_FRAMES + 1];        // kept rows of the batch in front of every frame start
+  __shared__ unsigned long long s_bal[PB / 64];
+  __shared__ unsigned hist[FULL_MAXC * FULL_MAXC];
+  __shared__ unsigned wave_n[PB / 64][3];
+  const int32_t* start_in = ws + nblk + 1;
+  const int32_t* bits = start_in + PMF_FOV_MAX_FRAMES + 1;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  if (tid <= B) {
+    const int64_t o = offsets[tid];
+    s_off[tid] = o;
+    s_moff[tid] = main_offsets[tid];
+    // a start at or behind the end has every kept row in front of it
+    s_g[tid] = o >= P ? (int64_t)ws[nblk] : o < 0 ? 0 : (int64_t)ws[o / PB] + start_in[tid];
+  }
+  if (conf)
+    for (int j = tid; j < C * C; j += PB) hist[j] = 0u;
+  __syncthreads();
+  if (blockIdx.x == 0 && tid < B) kept_count[tid] = s_g[tid + 1] - s_g[tid];
+  unsigned n[3] = {0u, 0u, 0u};
+  // a workgroup walks the count kernel's tiles of PB rows with the stride of the grid: one flush of the histogram and of the
+  // source counts per workgroup, however many rows the batch holds
+  for (int tile = blockIdx.x; tile < nblk; tile += gridDim.x) {
+    if (tid < PB / 64) {
+      const int32_t* w = bits + ((int64_t)tile * (PB / 64) + tid) * 2;
+      s_bal[tid] = (unsigned long long)(uint32_t)w[0] | ((unsigned long long)(uint32_t)w[1] << 32);
+    }
+    __syncthreads();
+    const int64_t i = tile * (int64_t)PB + tid;
+    if (i < P) {
+      const int b = fov_frame(s_off, B, i);
+      const bool k = (s_bal[wv] >> lane) & 1ull;
+      int before = __popcll(s_bal[wv] & ((1ull << lane) - 1ull));
+      for (int j = 0; j < wv; ++j) before += __popcll(s_bal[j]);
+      // unsigned arithmetic: a table that breaks the assumptions wraps instead of overflowing, and the index check decides
+      const uint64_t r = (uint64_t)((int64_t)ws[tile] + before) - (uint64_t)s_g[b];
+      uint32_t mw = 0u;
+      if (k && r < (uint64_t)s_moff[b + 1] - (uint64_t)s_moff[b]) {
+        const uint64_t at = (uint64_t)s_moff[b] + r;
+        if (at < (uint64_t)K_total) mw = main_ids[at] & 0xFFFFu;
+      }
+      uint32_t pred = mw;
+      int source = 0;
+      int pc = mw < (uint32_t)nlut ? lut[mw] : 0;
+      if (pc == 0) {
+        pred = sub_ids[i] & 0xFFFFu;
+        source = 1;
+        pc = pred < (uint32_t)nlut ? lut[pred] : 0;
+        if (pc == 0) {
+          pred = fill_id & 0xFFFFu;
+          source = 2;
+          pc = pred < (uint32_t)nlut ? lut[pred] : 0;
+        }
+      }
+      out[i] = pred;
+      n[0] += source == 0;
+      n[1] += source == 1;
+      n[2] += source == 2;
+      if (conf) {
+        const uint32_t g = gt[i] & 0xFFFFu;
+        const int t = g < (uint32_t)nlut ? lut[g] : 0;
+        if (t >= 0 && t < C && pc >= 0 && pc < C) atomicAdd(&hist[pc * C + t], 1u);
+      }
+    }
+    __syncthreads();                                        // the keep words change with the tile
+  }
+  if (counts) {                                             // the branch is uniform: every lane of the workgroup takes it
+    unsigned v[3] = {n[0], n[1], n[2]};
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      for (int d = 32; d >= 1; d >>= 1) v[c] += __shfl_down(v[c], d, 64);
+    if (lane == 0)
+      for (int c = 0; c < 3; ++c) wave_n[wv][c] = v[c];
+  }
+  __syncthreads();
+  if (counts && tid < 3) {
+    unsigned long long t = 0;
+    for (int j = 0; j < PB / 64; ++j) t += wave_n[j][tid];
+    if (t) atomicAdd(counts + tid, t);
+  }
+  if (conf)
+    for (int j = tid; j < C * C; j += PB)
+      if (hist[j]) atomicAdd(conf + j, (unsigned long long)hist[j]);
+}
+
+extern "C" int pmf_kitti_full_fill(const float* points, const int64_t* offsets, const int32_t* dims, int32_t B,
+                                   int64_t P_total, const double* proj, const uint32_t* main_ids,
+                                   const int64_t* main_offsets, int64_t K_total, const uint32_t* sub_ids, const uint32_t* gt,
+                                   const int32_t* lut, int32_t nlut, uint32_t fill_id, int32_t C, uint32_t* out,
+                                   uint8_t* keep, int64_t* kept_count, int64_t* counts, int64_t* conf, int32_t* blk_cnt,
+                                   pmf_stream_t s) {
+  hipStream_t st = (hipStream_t)s;
+  if (!points || !offsets || !dims || !proj || !main_offsets || !sub_ids || !lut || !out || !kept_count || !blk_cnt)
+    return PMF_E_ARG;
+  if (K_total < 0 || (K_total > 0 && !main_ids) || (conf && !gt)) return PMF_E_ARG;
+  if (B < 1 || B > PMF_FOV_MAX_FRAMES || P_total < 1 || C < 1 || C > FULL_MAXC || nlut < 1) return PMF_E_ARG;
+  if (((uintptr_t)points) & 15) return PMF_E_ARG;
+  if (P_total >= ((int64_t)1 << 31)) return PMF_E_UNSUPPORTED;
+  const int nblk = (int)cdiv64(P_total, PB);
+  const int nfill = nblk < FULL_GRID ? nblk : FULL_GRID;
+  hipLaunchKernelGGL(full_count_k, dim3(nblk), dim3(PB), 0, st, points, offsets, dims, B, P_total, proj, keep, blk_cnt, nblk);
+  hipLaunchKernelGGL(proj_scan_k, dim3(1), dim3(1024), 0, st, blk_cnt, nblk, blk_cnt + nblk);
+  hipLaunchKernelGGL(full_fill_k, dim3(nfill), dim3(PB), 0, st, offsets, B, P_total, blk_cnt, nblk, main_ids, main_offsets,
+                     K_total, sub_ids, gt, lut, nlut, fill_id, C, out, kept_count, (unsigned long long*)counts,
+                     (unsigned long long*)conf);
   PMF_LAUNCH_CHECK();
   return 0;
 }

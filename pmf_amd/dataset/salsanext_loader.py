@@ -15,7 +15,9 @@ from .preprocess import augmentor, projection
 
 
 class SalsaNextLoader(Dataset):
-    def __init__(self, dataset, config, data_len=-1, is_train=True, return_uproj=False, device="cuda"):
+    def __init__(self, dataset, config, data_len=-1, is_train=True, return_uproj=False, device="cuda", label_lut=None):
+        """label_lut: the raw id -> class table _eval_item scores with, whole (SemanticKITTI's moving classes have raw ids
+        up to 259); None = the 256-entry table _label_lut builds from the dataset"""
         self.dataset, self.config = dataset, config
         self.is_train, self.data_len, self.return_uproj = is_train, data_len, return_uproj
         self.device = torch.device(device)
@@ -36,6 +38,11 @@ class SalsaNextLoader(Dataset):
         self.proj_img_stds = torch.tensor(s["img_stds"], dtype=torch.float)
         self._mean_dev = self._stds_dev = None
         self._lut = None
+        if label_lut is not None:
+            t = np.ascontiguousarray(np.asarray(label_lut).reshape(-1), np.int32)
+            if t.shape[0] < 1:
+                raise ValueError("label_lut is empty")
+            self._lut = torch.from_numpy(t).to(self.device)
 
     def _label_lut(self):
         """int32[256] on the device: raw id -> class.  The dataset's map_name_from_general_index_to_segmentation_index (nuScenes)
@@ -57,8 +64,8 @@ class SalsaNextLoader(Dataset):
 
     def _eval_item(self, index):
         """evaluation item (is_train=False): dict(feature f32[5,H,W], label f32[H,W], mask i32[H,W], proj_range f32[H,W],
-        px / py int32[P] (column / row), depth f32[P], sem int32[P] raw ids, lut int32[256]), all on the device.  One
-        loadDataByIndex call and no host label pass: the raw ids go to the device once and the pixel labels are
+        px / py int32[P] (column / row), depth f32[P], sem int32[P] raw ids, lut int32[256] or the constructor's
+        label_lut), all on the device.  One loadDataByIndex call and no host label pass: the raw ids go to the device once and the pixel labels are
         lut[sem] there (the reference's loop loads every sweep a second time for its point labels)."""
         pointcloud, sem_label, _ = self.dataset.loadDataByIndex(index)
         pts = self.projection.to_device(pointcloud)

@@ -147,13 +147,14 @@ class SemanticKitti(object):
         return len(self.pointcloud_files)
 
 
-def write_prediction(dataset, index, pred, prediction_path):
+def write_prediction(dataset, index, pred, prediction_path, original_ids=False):
     """tasks/pmf_eval_semantickitti/infer.py:126-146: learning ids -> original ids (learning_map_inv), int32, one file
-    per frame under <prediction_path>/sequences/<seq>/predictions/<frame>.label; returns the path."""
+    per frame under <prediction_path>/sequences/<seq>/predictions/<frame>.label; returns the path.
+    original_ids: pred already holds original ids (mapped on the device) and is written as it is."""
     pred = np.asarray(pred).reshape(-1).astype(np.int32)
     seq_id, frame_id = dataset.parsePathInfoByIndex(index)
     out_dir = os.path.join(prediction_path, "sequences", seq_id, "predictions")
     os.makedirs(out_dir, exist_ok=True)
     path = os.path.join(out_dir, "{}.label".format(frame_id))
-    dataset.class_map_lut_inv[pred].tofile(path)
+    (pred if original_ids else dataset.class_map_lut_inv[pred]).tofile(path)
     return path
